@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Train-step throughput on MI355X (BASELINE.json metric), with roofline and CPU-baseline legs.
+"""Train-step throughput on MI355X (BASELINE.json metric); with `--full` also the roofline and CPU-baseline legs.
 
     python bench.py --gpus 1 --steps 100 --warmup 10
     python bench.py --gpus N ...            (no launcher: re-executes itself as N ranks under torch.distributed.run on a free port)
@@ -10,8 +10,14 @@ B = 32 clips of 3 s @ 16 kHz per GPU that is already resident in HBM (BASELINE c
 `--model dccrn_large` (configs[4]: 2x channels, rnn_units 512, B = 64 = 512 / 8 GPUs) and `--model fullsubnet` (configs[2], B = 64) print the same
 line for the other single-GPU configurations; `--batch 64` is the batch size of the north_star sentence.
 
-Order of the run (N = 1): the bounded CPU baseline first, then warm-up, the timed region, and the roofline leg, so that the GPU
-is busy for the last seconds of the process.
+A plain run sets up, warms up, times `--steps` steps, writes the outputs of the last timed step when `--dump-outputs DIR` is given, and
+prints the result line.  `--full` adds the side legs (N = 1): the bounded CPU baseline first, then warm-up, the timed region, the roofline
+leg and the side figures (B = 64 bf16, B = 32 fp32), so that the GPU is busy for the last seconds of the process.
+
+`--dump-outputs DIR`: what the caller of the timed path holds after the last timed step, as float32 .npy files - the loss of that step
+(`loss.npy`), every trainable parameter after its Adam update, flat in `named_parameters()` order (`parameters.npy`; above DUMP_MAX_PARAMS
+elements the same seeded sample of them in every run, in ascending position), and the BatchNorm running statistics (`bn_state.npy`, when
+the model has any).  Inputs and initial weights are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -33,6 +39,7 @@ PMC_ROUND = "r06"
 PMC_SUMMARY = os.path.join(ROOT, "profiles", f"{PMC_ROUND}_pmc_traffic.json")       # default workload; main() switches to <round>_pmc_traffic_<model>.json
 PMC_DEFAULT_BATCH = {"dccrn": 32, "dccrn_large": 64, "fullsubnet": 64}       # the batch each committed summary was collected at
 ALGO_GB_PER_UTT = 0.28                   # minimal fused activation traffic of one bf16 training step
+DUMP_MAX_PARAMS = 8 * 1024 * 1024        # --dump-outputs: parameters written in full up to this many (32 MB of float32), a seeded sample above
 
 
 CPU_B32 = False
@@ -48,13 +55,31 @@ def parse():
     ap.add_argument("--model", default="dccrn", choices=["dccrn", "dccrn_large", "fullsubnet"])
     ap.add_argument("--dtype", default=os.environ.get("SEFD_BENCH_DTYPE", "bf16"), choices=["fp32", "bf16"])
     ap.add_argument("--perceptual", default=None, choices=["LMS", "PMSQE"], help="DCCRN: loss = (SI-SNR + perceptual) / 2 (BASELINE configs[3] per-GPU shard)")
+    ap.add_argument("--full", action="store_true", help="also run the side legs: CPU baseline, roofline, the B = 64 bf16 and B = 32 fp32 side figures "
+                                                          "(each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-b32", action="store_true", help="also time the CPU baseline at B = 32 (1 warm-up + 5 timed steps, ~2 minutes)")
+    ap.add_argument("--cpu-b32", action="store_true", help="also time the CPU baseline at B = 32 (1 warm-up + 5 timed steps, ~2 minutes; with --full)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--from-host", action="store_true", help="side figure for DESIGN.md: every timed step first copies its batch from pinned host memory "
                                                                "(same stream, not overlapped) - the PCIe-inclusive rate; never the reported `value`")
-    ap.add_argument("--no-extra", action="store_true", help="skip the two side figures of the default run (B = 64 bf16, B = 32 fp32)")
+    ap.add_argument("--no-extra", action="store_true", help="skip the two side figures of the --full run (B = 64 bf16, B = 32 fp32)")
     return ap.parse_args()
+
+
+def dump_outputs(d, model, loss):
+    """--dump-outputs: the loss of the last timed step, the updated parameters and the BatchNorm running statistics, as float32 .npy files."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "loss.npy"), np.asarray([float(loss)], dtype=np.float32))
+    params = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]).cpu().numpy()
+    if params.size > DUMP_MAX_PARAMS:
+        idx = np.sort(np.random.default_rng(0).choice(params.size, DUMP_MAX_PARAMS, replace=False))
+        params = params[idx]
+    np.save(os.path.join(d, "parameters.npy"), params)
+    bn = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+    if bn:
+        np.save(os.path.join(d, "bn_state.npy"), torch.cat(bn).cpu().numpy())
 
 
 def make_batch(B, L, rank, device):
@@ -295,7 +320,7 @@ def main():
     large = args.model == "dccrn_large"
     kn, ru = ((64, 128, 256, 512, 512, 512), 512) if large else ((32, 64, 128, 256, 256, 256), 256)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "dccrn" and not args.perceptual:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "dccrn" and not args.perceptual:
         cpu = cpu_baseline(L, kn, ru)                    # first: the GPU legs then run back to back until the process ends
     torch.manual_seed(0)
     if args.model == "fullsubnet":
@@ -356,6 +381,8 @@ def main():
         per_rank_ms = [round(dt / args.steps * 1e3, 3)]
     dt = float(tmax)
     lossv = float(loss)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, loss)
     out = None
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -367,7 +394,7 @@ def main():
                                          if dist_on else "none"),
                           "per_rank_ms": per_rank_ms},
                "final_loss": round(lossv, 5)}
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             if args.model == "fullsubnet":
                 plan, arenas = next(v for k, v in model._runtimes.items() if k[0] == "fsn")
             else:
@@ -391,7 +418,7 @@ def main():
                                                    traffic_over_algorithmic=round(tot / (ALGO_GB_PER_UTT * 1e9 * B), 2))
         if cpu is not None:
             out["cpu_baseline"] = cpu
-        if world == 1 and not dist_on and args.model == "dccrn" and not args.perceptual and args.batch is None and args.dtype == "bf16" and not args.no_extra:
+        if args.full and world == 1 and not dist_on and args.model == "dccrn" and not args.perceptual and args.batch is None and args.dtype == "bf16" and not args.no_extra:
             # side figures of the same workload, same code path, timed the same way (shorter): the north_star batch (64) and the dtype that
             # carries the 1e-3 parity criterion (fp32 activations: fp32 MFMA, 1/16 of the bf16 matrix rate)
             del opt, model

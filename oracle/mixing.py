@@ -1,6 +1,6 @@
 """Oracle (test infrastructure): the reference's offline SNR mixing restated (generate_noisy_data.py:46-67 `generate_noisy_wav`), with the
-random segment start passed in instead of drawn.  Pinned by running the reference function itself under a patched np.random.randint
-(tests/test_oracle_mixing.py, build container only) - the GPU test compares sefd_amd.dataloader.mix_snr with this."""
+random segment start passed in instead of drawn.  Pinned to outputs of the reference function itself under a patched np.random.randint
+(tests/test_oracle_mixing.py, goldens from tests/golden/make_mixing_golden.py) - the GPU test compares sefd_amd.dataloader.mix_snr with this."""
 import numpy as np
 
 

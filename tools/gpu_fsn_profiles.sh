@@ -15,5 +15,5 @@ pmc fullsubnet --model fullsubnet
 cp $O/fin_pmc_fullsubnet.json profiles/r05_pmc_traffic_fullsubnet.json 2>/dev/null
 TIMELINE_MARK=fsn_in_kernel:1 python tools/timeline.py $O/fin_prof_fullsubnet/k_kernel_trace.csv 1 v > $O/fin_timeline_fullsubnet.txt 2>&1
 find $O -name "k_kernel_trace.csv" -size +20M -delete 2>/dev/null
-timeout 600 python bench.py --model fullsubnet --no-cpu-baseline > $O/fin_bench_fullsubnet.log 2>&1; tail -1 $O/fin_bench_fullsubnet.log | cut -c60-180
+timeout 600 python bench.py --full --model fullsubnet --no-cpu-baseline > $O/fin_bench_fullsubnet.log 2>&1; tail -1 $O/fin_bench_fullsubnet.log | cut -c60-180
 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-extra 2>&1 | tail -1 | cut -c60-180

@@ -24,10 +24,10 @@ pmc fullsubnet --model fullsubnet
 cp $O/fin_pmc_fullsubnet.json profiles/r06_pmc_traffic_fullsubnet.json 2>/dev/null
 TIMELINE_MARK=fsn_in_kernel:1 python tools/timeline.py $O/fin_prof_fullsubnet/k_kernel_trace.csv 1 v > $O/fin_timeline_fullsubnet.txt 2>&1
 find $O -name "k_kernel_trace.csv" -size +20M -delete 2>/dev/null
-timeout 900 python bench.py > $O/fin_bench_default.log 2>&1; tail -1 $O/fin_bench_default.log | cut -c1-250
+timeout 900 python bench.py --full > $O/fin_bench_default.log 2>&1; tail -1 $O/fin_bench_default.log | cut -c1-250
 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-extra > $O/fin_bench_driver.log 2>&1; tail -1 $O/fin_bench_driver.log | cut -c60-180
-timeout 600 python bench.py --batch 64 --no-cpu-baseline > $O/fin_bench_B64.log 2>&1; tail -1 $O/fin_bench_B64.log | cut -c60-180
-timeout 600 python bench.py --model dccrn_large --no-cpu-baseline > $O/fin_bench_dccrn_large.log 2>&1; tail -1 $O/fin_bench_dccrn_large.log | cut -c60-180
-timeout 600 python bench.py --model fullsubnet --no-cpu-baseline > $O/fin_bench_fullsubnet.log 2>&1; tail -1 $O/fin_bench_fullsubnet.log | cut -c60-180
-timeout 600 python bench.py --perceptual PMSQE --no-cpu-baseline > $O/fin_bench_pmsqe.log 2>&1; tail -1 $O/fin_bench_pmsqe.log | cut -c60-180
-timeout 600 python bench.py --perceptual LMS --no-cpu-baseline > $O/fin_bench_lms.log 2>&1; tail -1 $O/fin_bench_lms.log | cut -c60-180
+timeout 600 python bench.py --full --batch 64 --no-cpu-baseline > $O/fin_bench_B64.log 2>&1; tail -1 $O/fin_bench_B64.log | cut -c60-180
+timeout 600 python bench.py --full --model dccrn_large --no-cpu-baseline > $O/fin_bench_dccrn_large.log 2>&1; tail -1 $O/fin_bench_dccrn_large.log | cut -c60-180
+timeout 600 python bench.py --full --model fullsubnet --no-cpu-baseline > $O/fin_bench_fullsubnet.log 2>&1; tail -1 $O/fin_bench_fullsubnet.log | cut -c60-180
+timeout 600 python bench.py --full --perceptual PMSQE --no-cpu-baseline > $O/fin_bench_pmsqe.log 2>&1; tail -1 $O/fin_bench_pmsqe.log | cut -c60-180
+timeout 600 python bench.py --full --perceptual LMS --no-cpu-baseline > $O/fin_bench_lms.log 2>&1; tail -1 $O/fin_bench_lms.log | cut -c60-180
