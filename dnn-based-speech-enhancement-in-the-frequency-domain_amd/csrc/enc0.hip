@@ -25,13 +25,6 @@ namespace {
 constexpr int kE0Frames = 8;       // output frames per workgroup of the forward kernel
 constexpr int kE0Pitch = 132;      // floats per de-interleaved quarter of a staged frame (516 / 4 = 129 used + zero tail)
 
-// the descriptor has the form these kernels execute: one fp32 source, two runs (frame t - 1, frame t) of 10 floats at 4 floats per output bin
-__host__ __device__ inline bool enc0_form(const RunGemm& d) {
-  return (d.flags & kRunEnc0) && d.xdt == DT_F32 && d.nseg == 2 && d.seg[0].src == 0 && d.seg[1].src == 0 && d.seg[0].len == 10 && d.seg[1].len == 10 &&
-         d.seg[0].dt == -1 && d.seg[1].dt == 0 && d.seg[0].off == -4 && d.seg[1].off == -4 && d.fstride[0] == 4 && d.base[0] == 4 && d.rowlen[0] == 512 &&
-         d.Fo == 128 && d.tstride[0] == 516 && (d.N == 16 || d.N == 32 || d.N == 64) && d.n2 == 0;
-}
-
 }  // namespace
 
 template <int CO>
@@ -283,7 +276,7 @@ __global__ __launch_bounds__(256) void enc0_wgrad_kernel(const RunGemm d, const 
 }
 
 bool launch_enc0_fwd(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  if (!enc0_form(d) || d.ydt != DT_BF16 || !(d.flags & kRunYAligned) || (d.flags & (kRunAccum | kRunBnBwd))) return false;
+  if (!(d.flags & kRunEnc0) || !enc0_accepts(d, false)) return false;          // (sefd_desc.h)
   const int B = d.M / (d.Tout * d.Fo);
   const dim3 grid((unsigned)(B * ((d.Tout + kE0Frames - 1) / kE0Frames)));
   if (d.N <= 16) hipLaunchKernelGGL(enc0_fwd_kernel<16>, grid, dim3(256), 0, st, d, ab);
@@ -293,7 +286,7 @@ bool launch_enc0_fwd(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
 }
 
 bool launch_enc0_wgrad(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  if (!enc0_form(d) || d.ydt != DT_BF16 || d.y_fstride % 8 != 0 || d.y_off % 8 != 0) return false;
+  if (!(d.flags & kRunEnc0) || !enc0_accepts(d, true)) return false;
   const dim3 grid((unsigned)d.nsplit);
   const bool fuse = (d.flags & kRunDyFromBn) != 0;
 #define SEFD_E0W(CO)                                                                                              \

@@ -418,6 +418,7 @@ void finalize_rungemms(Builder& b, Plan* P) {
                         g.y_bstride % 8 == 0 && (g.y.off % 16) == 0;
         g.flags = (g.flags & ~kRunYAligned) | (ya ? kRunYAligned : 0);
       }
+      if (!enc0_accepts(g, op.kind == OP_WGRAD) && P->error.empty()) P->error = "first-layer descriptor (kRunEnc0 / kRunDyFromBn) without a kernel";
     }
   // Wide-tile kernel (cgemm256.hip) for the bf16 layers that carry the FLOPs: N a multiple of 256, LDS-DMA-able runs, enough rows.
   // Its weights are packed K-tile major (kRunWTile32): a property of the packed BUFFER, so it is chosen only when every GEMM
@@ -530,7 +531,8 @@ void finalize_rungemms(Builder& b, Plan* P) {
   }
   // SyncBN (cfg.bn_world > 1): every training-mode BN_FINALIZE becomes "publish this rank's sums" + "statistics from the
   // all-reduced sums" with a sync point in between; every BN_BWD_FINALIZE is followed by a sync point on its totals.
-  // Counts become global.  The caller (models.py / hostsim tests) runs the op ranges between sync points and all-reduces.
+  // Counts become global: every descriptor that carries a BatchNorm count (BN_FINALIZE, BN_BWD_APPLY, the kRunDyFromBn WGRAD) is scaled here.
+  // The caller (models.py / hostsim tests) runs the op ranges between sync points and all-reduces.
   const int world = P->cfg.bn_world;
   if (world > 1 && P->cfg.training) {
     int k = 0;
@@ -551,6 +553,9 @@ void finalize_rungemms(Builder& b, Plan* P) {
           P->syncs.push_back(SyncPoint{phase, (int32_t)out.size() - 1, op.bnb.totals, 2 * (int64_t)op.bnb.r.C, 0});
         } else if (op.kind == OP_BN_BWD_APPLY) {
           op.bnb.count *= world;
+          out.push_back(op);
+        } else if (op.kind == OP_WGRAD && (op.g.flags & kRunDyFromBn)) {
+          op.g.bnb_inv_count /= (float)world;       // the BatchNorm backward fused into enc0's weight gradient divides the all-reduced totals
           out.push_back(op);
         } else {
           out.push_back(op);
@@ -1814,7 +1819,8 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       // First layer on the spectrum (enc0.hip): it has no input gradient, so its BatchNorm input gradient dy is read by the weight gradient alone -
       // BN_BWD_APPLY is not planned, the weight-gradient kernel takes dz through the BatchNorm + PReLU backward as it loads it (kRunDyFromBn) and runs on
       // the MAIN stream right behind BN_BWD_FINALIZE: apply (117 us) -> fold -> weight gradient (52 us) was the serial tail of the step.  ENC0_BNFUSE=0: off
-      const bool dy_fused = i == 0 && (enc[0].f[0].flags & kRunEnc0) && !cbn && !(tune_str("ENC0_BNFUSE") && atoi(tune_str("ENC0_BNFUSE")) == 0);
+      const bool dy_fused = i == 0 && (enc[0].f[0].flags & kRunEnc0) && enc0_accepts(enc[0].f[0], true) && !cbn &&    // (its weight gradient's form: sefd_desc.h)
+                            !(tune_str("ENC0_BNFUSE") && atoi(tune_str("ENC0_BNFUSE")) == 0);
       bn_bwd(100 + i, ency[i], d_encz[i], cfg.skip ? d_skip[i] : b.none(), enc_mi[i], pp, Co, enc[i].R, (int64_t)T * Fo, 0, d_ency[i], nm, &bnb_enc[i], dy_fused);
       // the folds of enc5 .. enc1 go in front of the LAST weight gradient on its lane (its input is the last thing the dgrad chain produces,
       // the lane usually waits for it): the fold in front of the final UNPACK then covers one thin layer
@@ -1841,6 +1847,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
             g.bnb_y = ency[i]; g.bnb_mi = enc_mi[i];
             g.bnb_gamma = b.pptr(pp + ".1.weight"); g.bnb_beta = b.pptr(pp + ".1.bias"); g.bnb_slope = b.pptr(pp + ".2.weight");
             g.bnb_bstride = g.y_bstride; g.bnb_tstride = g.y_tstride; g.bnb_fstride = g.y_fstride; g.bnb_off = g.y_off;
+            // per-rank count: like every descriptor that carries a BatchNorm count, this one must be scaled by the SyncBN post-pass (finalize_rungemms)
             g.bnb_totals = last_bnb.totals; g.bnb_inv_count = (float)(1.0 / last_bnb.count);
             break;
           }

@@ -1280,8 +1280,18 @@ static void launch_rungemm_t(const RunGemm& d, const ArenaBases& ab, hipStream_t
   else hipLaunchKernelGGL((rungemm_kernel<TA, 32, false>), dim3(grid), dim3(256), 0, st, d, ab);
 }
 
+// A descriptor that carries kRunEnc0 / kRunDyFromBn but that enc0.hip declined (sefd_desc.h enc0_accepts): no generic kernel reads those flags, so
+// one would compute a wrong result silently.  Nothing is launched for it; the plan's status word is raised instead (the run after it and the
+// guarded Adam see it, as after a kernel that gave up).  The planner and the host simulator check the same predicate on every descriptor.
+__global__ void refuse_launch_kernel(int* host_word, int* dev_word) { set_status(host_word, dev_word); }
+
+static void refuse_launch(const ArenaBases& ab, hipStream_t st) {
+  hipLaunchKernelGGL(refuse_launch_kernel, dim3(1), dim3(1), 0, st, ab.status, ab.dstatus);
+}
+
 void launch_rungemm(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
   if (launch_enc0_fwd(d, ab, st)) return;                  // first encoder layer of the bf16 plans, on the fp32 spectrum (enc0.hip)
+  if (d.flags & (kRunEnc0 | kRunDyFromBn)) { refuse_launch(ab, st); return; }
   if (launch_cgemm256(d, ab, st)) return;                  // wide-tile kernel for the N >= 128 bf16 layers (cgemm256.hip)
   if (launch_rundirect(d, ab, st)) return;                 // direct-operand kernel for the thin bf16 layers (thin.hip)
   if (d.xdt == DT_BF16) launch_rungemm_t<bf16_t>(d, ab, st);
@@ -1324,6 +1334,7 @@ static void launch_wgrad_dma(const RunGemm& d, const ArenaBases& ab, hipStream_t
 
 void launch_wgrad(const RunGemm& d0, const ArenaBases& ab, hipStream_t st) {
   if (launch_enc0_wgrad(d0, ab, st)) return;               // ... and its weight gradient
+  if (d0.flags & (kRunEnc0 | kRunDyFromBn)) { refuse_launch(ab, st); return; }
   if (launch_wgrad_rank(d0, ab, st)) return;               // N <= 4 outputs over a contiguous array
   RunGemm d = d0;
 #ifdef SEFD_TUNING

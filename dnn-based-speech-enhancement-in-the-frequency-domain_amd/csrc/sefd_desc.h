@@ -462,6 +462,23 @@ struct Op {
 #else
 #define SEFD_HD
 #endif
+// ---- first encoder layer on the fp32 spectrum (kRunEnc0, enc0.hip): the descriptor form its two kernels execute - one fp32 source, two runs
+// (frame t - 1, frame t) of 10 floats at 4 floats per output bin
+SEFD_HD inline bool enc0_form(const RunGemm& d) {
+  return (d.flags & kRunEnc0) && d.xdt == DT_F32 && d.nseg == 2 && d.seg[0].src == 0 && d.seg[1].src == 0 && d.seg[0].len == 10 && d.seg[1].len == 10 &&
+         d.seg[0].dt == -1 && d.seg[1].dt == 0 && d.seg[0].off == -4 && d.seg[1].off == -4 && d.fstride[0] == 4 && d.base[0] == 4 && d.rowlen[0] == 512 &&
+         d.Fo == 128 && d.tstride[0] == 516 && (d.N == 16 || d.N == 32 || d.N == 64) && d.n2 == 0;
+}
+// What launch_enc0_fwd (RUNGEMM) / launch_enc0_wgrad (WGRAD) execute.  No other kernel reads kRunEnc0 or kRunDyFromBn, so a descriptor that
+// carries either flag MUST pass this: the planner refuses a plan where one does not, the host simulator fails its run, and the launchers
+// raise the plan's status word instead of launching a generic kernel that would ignore the flags.
+SEFD_HD inline bool enc0_accepts(const RunGemm& d, bool wgrad) {
+  if (!(d.flags & (kRunEnc0 | kRunDyFromBn))) return true;
+  if (!enc0_form(d) || d.ydt != DT_BF16) return false;
+  if (wgrad) return d.y_fstride % 8 == 0 && d.y_off % 8 == 0;
+  return (d.flags & kRunYAligned) && !(d.flags & (kRunAccum | kRunBnBwd | kRunDyFromBn));
+}
+
 struct RowsJob { int layer, chunk, block, tb, te; };      // frames [tb, te) of row block `block`
 // lstm_fwd_rows_pair_kernel: two stacked layers x C time chunks x nblk row blocks, wavefront order: segment 0 = L chunk 0; segments 1 + 2p, 2 + 2p =
 // L chunk p + 1, U chunk p; last segment = U chunk C - 1.  L(c, j) reads L(c - 1, j); U(c, j) reads U(c - 1, j) and L(c, j): all in earlier segments.

@@ -1205,10 +1205,24 @@ extern "C" int hostsim_run(const void* ops_, int first, int last, void* const* a
   const Op* ops = (const Op*)ops_;
   AB ab;
   for (int a = 0; a < A_COUNT; ++a) ab.p[a] = (char*)arenas[a];
-  for (int i = first; i < last; ++i) run_op(ops[i], ab);
+  for (int i = first; i < last; ++i) {
+    // a first-layer descriptor that the enc0 kernels would decline has no kernel on the device (sefd_desc.h enc0_accepts): fail the run
+    if ((ops[i].kind == OP_RUNGEMM || ops[i].kind == OP_WGRAD) && !enc0_accepts(ops[i].g, ops[i].kind == OP_WGRAD)) {
+      std::fprintf(stderr, "hostsim: op %d (kind %d, tag %d) carries kRunEnc0 / kRunDyFromBn but fails enc0_accepts\n", i, ops[i].kind, ops[i].tag);
+      return -1;
+    }
+    run_op(ops[i], ab);
+  }
   return 0;
 }
 extern "C" int hostsim_op_size() { return (int)sizeof(Op); }
+// test hook: enc0_accepts on a copy of RUNGEMM / WGRAD descriptor `op_` with y_off moved by `dy_off` (-1: not such an op)
+extern "C" int hostsim_enc0_accepts(const void* op_, int dy_off) {
+  Op op = *(const Op*)op_;
+  if (op.kind != OP_RUNGEMM && op.kind != OP_WGRAD) return -1;
+  op.g.y_off += dy_off;
+  return enc0_accepts(op.g, op.kind == OP_WGRAD) ? 1 : 0;
+}
 // job order of the ticket-drawn recurrence launches (sefd_desc.h rows_pair_job / rows_bwd_job): out = {layer, chunk, block, tb, te}
 extern "C" void hostsim_rows_job(int bwd, int job, int nblk, int C, int T, int* out) {
   const RowsJob r = bwd ? rows_bwd_job(job, nblk, C, T) : rows_pair_job(job, nblk, C, T);

@@ -82,14 +82,14 @@ def test_shard_batch_partitions():
 SMALL = dict(kernel_num=(16, 32, 32, 64, 64, 64), rnn_units=128)
 
 
-def _syncbn_worker(rank, world, port, q, sisdr=False):
+def _syncbn_worker(rank, world, port, q, sisdr=False, act_dtype="fp32"):
     """Each rank interprets a SyncBN plan (bn_world = 2) for its half of the batch with the host simulator; the statistics
     buffers are all-reduced over gloo at the plan's sync points - the same call sequence models.py issues on the GPUs."""
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from oracle.dccrn import DCCRNConfig, dccrn_state_shapes
     from oracle.weights import formula_state_dict
-    from simutil import PHASE_BWD, PHASE_FWD, Plan, fill_params, read_params, sim_run
+    from simutil import PHASE_BWD, PHASE_FWD, Plan, check_syncbn_result, fill_params, read_params, sim_run, unit_slopes
     from sefd_amd.plan import ARENA_GRAD, ARENA_STATE
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -98,6 +98,8 @@ def _syncbn_worker(rank, world, port, q, sisdr=False):
         B, L = 4, 3000
         Bl = B // world
         P = formula_state_dict(dccrn_state_shapes(DCCRNConfig(masking_mode="C", **SMALL)))
+        if act_dtype != "fp32":
+            P = unit_slopes(P)                                   # bf16: no PReLU branch flips between the two statistics orders (simutil.unit_slopes)
         x, _ = make_signals(B, L)
         torch.manual_seed(7)
         gw = torch.randn(B, L)
@@ -144,7 +146,7 @@ def _syncbn_worker(rank, world, port, q, sisdr=False):
             return wav, read_params(plan, ar, ARENA_GRAD), read_params(plan, ar, ARENA_STATE, plan.state)
 
         lo, hi = rank * Bl, (rank + 1) * Bl
-        plan = Plan(Bl, L, masking_mode="C", bn_world=world, **SMALL)
+        plan = Plan(Bl, L, masking_mode="C", bn_world=world, act_dtype=act_dtype, **SMALL)
         assert len(plan.sync_points()) == 2 * 11                 # 11 BatchNorm layers, forward and backward
         wav, grads, state = run(plan, x[lo:hi], gw[lo:hi], True, clean[lo:hi] if sisdr else None)
         flat = torch.cat([grads[k].reshape(-1) for k in grads])
@@ -154,7 +156,7 @@ def _syncbn_worker(rank, world, port, q, sisdr=False):
             sharded_loss = run.loss
         res = None
         if rank == 0:
-            full = Plan(B, L, masking_mode="C", **SMALL)
+            full = Plan(B, L, masking_mode="C", act_dtype=act_dtype, **SMALL)
             assert len(full.sync_points()) == 0
             fwav, fgrads, fstate = run(full, x, gw, False, clean if sisdr else None)
             fflat = torch.cat([fgrads[k].reshape(-1) for k in fgrads])
@@ -165,28 +167,50 @@ def _syncbn_worker(rank, world, port, q, sisdr=False):
                        state=max(float((state[k] - fstate[k]).abs().max() / (fstate[k].abs().max() + 1e-12)) for k in fstate))
             if sisdr:
                 res["loss"] = abs(sharded_loss - run.loss) / abs(run.loss)
+            if act_dtype != "fp32":                              # per tensor, at the bars of the single-process emulation (simutil.check_syncbn_result)
+                gr, o = {}, 0
+                for k in fgrads:
+                    gr[k] = flat[o:o + fgrads[k].numel()].reshape(fgrads[k].shape).double()
+                    o += fgrads[k].numel()
+                try:
+                    check_syncbn_result(dict(full=dict(out={"out_wav": fwav[lo:hi]}, grad={k: v.double() for k, v in fgrads.items()}, state=fstate),
+                                             ranks=dict(out={"out_wav": wav}, grad=gr, state=[state])), act_dtype)
+                    res["per_tensor"] = "ok"
+                except AssertionError as e:
+                    res["per_tensor"] = repr(e)
         q.put((rank, res))
     finally:
         dist.destroy_process_group()
 
 
-def test_world2_syncbn_equals_single_process_big_batch():
-    """SURVEY 8e: 2 ranks x 2 utterances with SyncBN == the reference's single process with batch 4 (outputs, gradients
-    after the sum exchange, BatchNorm running statistics)."""
+def _run_syncbn(act_dtype):
     world = 2
     port = _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_syncbn_worker, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_syncbn_worker, args=(r, world, port, q, False, act_dtype)) for r in range(world)]
     for p in procs:
         p.start()
     for p in procs:
         p.join(600)
         assert p.exitcode == 0
     res = dict(q.get(timeout=5) for _ in range(world))
-    r0 = res[0]
+    return res[0]
+
+
+def test_world2_syncbn_equals_single_process_big_batch():
+    """SURVEY 8e: 2 ranks x 2 utterances with SyncBN == the reference's single process with batch 4 (outputs, gradients
+    after the sum exchange, BatchNorm running statistics)."""
+    r0 = _run_syncbn("fp32")
     assert r0["wav"] < 2e-5 and r0["state"] < 2e-5, r0
     assert r0["grad"] < 2e-4, r0
+
+
+def test_world2_syncbn_bf16_equals_single_process_big_batch():
+    """The same in bf16 (the product default, where enc0's weight gradient runs the BatchNorm backward itself: kRunDyFromBn), per tensor at the
+    bars of simutil.check_syncbn_result."""
+    r0 = _run_syncbn("bf16")
+    assert r0["per_tensor"] == "ok", r0
 
 
 def test_world2_sisdr_sharded_equals_single_process_big_batch():

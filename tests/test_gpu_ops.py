@@ -334,72 +334,54 @@ def test_adam_step_matches_torch_formula():
 
 
 def test_syncbn_plans_two_ranks_emulated_on_one_gpu():
-    """SyncBN op modes on the HIP kernels: two bn_world=2 plans (the two "ranks", 2 utterances each) are advanced in lock
+    """SyncBN op modes on the HIP kernels, fp32, two ranks of the small DCCRN (the other dtypes, sizes, worlds and BatchNorm-backward arms:
+    test_syncbn_plans_ranks_emulated_on_one_gpu_cases)."""
+    _syncbn_ranks_on_one_gpu("fp32", (16, 32, 32, 64, 64, 64), 2, None)
+
+
+# bf16 at world 4 (one utterance per rank) is held on the host simulator (test_syncbn_ranks_equal_big_batch_plan): on the kernels its rounding
+# flips are not reproducible from run to run and reached 6.9e-2 (encoder.0.1.bias) - above every bf16 bar; fp32 carries world 4 here.
+@pytest.mark.parametrize("dtype,kn,world,knob", [("fp32", (16, 32, 32, 64, 64, 64), 4, None),
+                                                 ("fp32", (32, 64, 128, 256, 256, 256), 2, None),
+                                                 ("bf16", (16, 32, 32, 64, 64, 64), 2, None),          # enc0_wgrad_kernel<16, true>: fused BatchNorm backward
+                                                 ("bf16", (32, 64, 128, 256, 256, 256), 2, None),      # enc0_wgrad_kernel<32, true>
+                                                 ("bf16", (16, 32, 32, 64, 64, 64), 2, ("BN_FUSE", "2"))])  # backward sums from the GEMM epilogues
+def test_syncbn_plans_ranks_emulated_on_one_gpu_cases(dtype, kn, world, knob):
+    _syncbn_ranks_on_one_gpu(dtype, kn, world, knob)
+
+
+def _syncbn_ranks_on_one_gpu(dtype, kn, world, knob):
+    """SyncBN op modes on the HIP kernels: `world` bn_world plans (the "ranks", B / world utterances each) are advanced in lock
     step on one GPU, their statistics buffers summed at every sync point (what RCCL does between the ranks), and must
-    reproduce the single plan over all 4 utterances: outputs, gradients (summed), BatchNorm running statistics."""
-    from simutil import PHASE_BWD, PHASE_FWD, Plan, fill_params, read_params
-    from sefd_amd.plan import ARENA_GRAD, ARENA_STATE
-    kn, ru, B, L = (16, 32, 32, 64, 64, 64), 128, 4, 3000
+    reproduce the single plan over all B utterances: outputs, gradients (summed), BatchNorm running statistics.  Bars and the
+    tensors checked: simutil.check_syncbn_result (the host-simulator test of the same comparison: test_syncbn_ranks_equal_big_batch_plan)."""
+    from simutil import DEFAULT_KN, DEFAULT_KN_ONLY, KIND_WGRAD, RUN_DY_FROM_BN, PHASE_BWD, Plan, check_syncbn_result, syncbn_vs_big_batch, unit_slopes
+    ru = 128 if kn[0] == 16 else 256
+    B, L = 4, (3000 if kn[0] == 16 else 2400)
+    if knob:
+        knobs.set(*knob)
     P = formula_state_dict(dccrn_state_shapes(DCCRNConfig(masking_mode="C", kernel_num=kn, rnn_units=ru)))
     # PReLU slopes = 1 (identity): the two runs sum their statistics in different orders, so activations differ by ~1e-7, and ONE element
     # whose pre-activation lies that close to zero then takes different PReLU branches in the backward - which moves a whole layer's sums
     # by (1 - slope) * dz of that element (seen: 3e-3 of a layer's sum(dbn), one flip among 1.1 M elements; expected ~0.5 flips per run).
     # That discontinuity is not what this test is about (the SyncBN plumbing is); the kernels' PReLU branches are pinned by the per-op test.
-    for k in P:
-        if k.endswith(".2.weight"):
-            P[k] = torch.ones_like(P[k])
+    P = unit_slopes(P)
     x, _ = make_signals(B, L)
     torch.manual_seed(7)
     gw = torch.randn(B, L)
-    stream = torch.cuda.current_stream().cuda_stream
 
-    def prep(plan, xs):
-        ar = plan.alloc_arenas("cuda")
-        fill_params(plan, ar, P)
-        plan.io(ar, "wav", xs.shape).copy_(xs.cuda())
-        return ar
-
-    def seed_grad(plan, ar, gs):
-        plan.io(ar, "grad_wav", gs.shape).copy_(gs.cuda())
-        plan.io(ar, "grad_real", (gs.shape[0], plan.NF, plan.T)).zero_()
-        plan.io(ar, "grad_imag", (gs.shape[0], plan.NF, plan.T)).zero_()
-
-    full = Plan(B, L, masking_mode="C", kernel_num=kn, rnn_units=ru)
-    far = prep(full, x)
-    full.run(PHASE_FWD, far, stream)
-    seed_grad(full, far, gw)
-    full.run(PHASE_BWD, far, stream)
-    ranks = [Plan(B // 2, L, masking_mode="C", kernel_num=kn, rnn_units=ru, bn_world=2) for _ in range(2)]
-    ars = [prep(p, x[2 * r:2 * r + 2]) for r, p in enumerate(ranks)]
-    for ph in (PHASE_FWD, PHASE_BWD):
-        if ph == PHASE_BWD:
-            for r in range(2):
-                seed_grad(ranks[r], ars[r], gw[2 * r:2 * r + 2])
-        cur = 0
-        for sph, op, a, off, cnt, dtype in ranks[0].sync_points():
-            if sph != ph:
-                continue
-            views = []
-            for r in range(2):
-                ranks[r].run(ph, ars[r], stream, cur, op + 1)
-                nb = cnt * (8 if dtype == torch.float64 else 4)
-                views.append(ars[r][a].view(torch.uint8)[off:off + nb].view(dtype))
-            tot = views[0] + views[1]
-            views[0].copy_(tot)
-            views[1].copy_(tot)
-            cur = op + 1
-        for r in range(2):
-            ranks[r].run(ph, ars[r], stream, cur, ranks[r].num_ops(ph))
-    torch.cuda.synchronize()
-    fw = full.io(far, "out_wav", (B, L))
-    for r in range(2):
-        assert rel_err(ranks[r].io(ars[r], "out_wav", (2, L)), fw[2 * r:2 * r + 2]) < 1e-4
-    fg = read_params(full, far, ARENA_GRAD)
-    g0, g1 = read_params(ranks[0], ars[0], ARENA_GRAD), read_params(ranks[1], ars[1], ARENA_GRAD)
-    for k in fg:
-        if k.endswith("conv.bias") and not k.startswith("decoder.5."):
-            continue
-        assert rel_err(g0[k] + g1[k], fg[k]) < 1e-3, k
-    fs, s0 = read_params(full, far, ARENA_STATE, full.state), read_params(ranks[0], ars[0], ARENA_STATE, ranks[0].state)
-    for k in fs:
-        assert rel_err(s0[k], fs[k]) < 1e-4, k
+    def make_plan(b, bn_world):
+        return Plan(b, L, masking_mode="C", kernel_num=kn, rnn_units=ru, act_dtype=dtype, bn_world=bn_world)
+    res = syncbn_vs_big_batch(make_plan, P, {"wav": x}, {"grad_wav": gw}, world, device="cuda", stream=torch.cuda.current_stream().cuda_stream)
+    if dtype == "bf16":
+        plan = res["ranks"]["plans"][0]
+        fused = [i for i in range(plan.num_ops(PHASE_BWD)) if plan.op_info(PHASE_BWD, i)["kind"] == KIND_WGRAD and plan.op_info(PHASE_BWD, i)["tag"] == 100
+                 and plan.op_info(PHASE_BWD, i)["flags"] & RUN_DY_FROM_BN]
+        assert len(fused) == 1, fused
+    # bf16 weight / bias gradients on the kernels: 5e-2.  The kernels accumulate in other orders than the host simulator, and the rounding flips of
+    # this comparison reached 3.3e-2 there (encoder.0.0.real_conv.weight, kn[0] = 32); the missing world factor of a BatchNorm count moves the first
+    # layer's gradient by 0.3 .. 0.9
+    errs = check_syncbn_result(res, dtype, only=DEFAULT_KN_ONLY if kn == DEFAULT_KN and dtype == "bf16" else None, grad_bar=5e-2 if dtype == "bf16" else None)
+    worst = sorted(errs.items(), key=lambda kv: -kv[1])[:8]
+    with open(_report_path(f"syncbn_{dtype}_kn{kn[0]}_w{world}_{knob[0] if knob else 'default'}.txt"), "w") as f:
+        f.write("\n".join(f"{k} {v:.3e}" for k, v in worst) + "\n")

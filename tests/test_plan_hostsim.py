@@ -10,6 +10,7 @@ from oracle.frontend import analysis_kernel, synthesis_kernel, ola_normaliser
 from oracle.losses import main_loss
 from oracle.weights import formula_state_dict, test_signals as make_signals
 from simutil import (ARENA_PARAM, PHASE_BWD, PHASE_FWD, Plan, act_to_nchw, fill_params, read_params, sim_run, spec_to_ref)
+from simutil import DEFAULT_KN, DEFAULT_KN_ONLY, KIND_WGRAD, RUN_DY_FROM_BN, check_syncbn_result, unit_slopes
 from sefd_amd.plan import ARENA_GRAD, ARENA_STATE
 from util import knobs, rel_err
 
@@ -614,3 +615,61 @@ def test_rows_job_order_is_a_deadlock_free_schedule(nblk, C, T):
             assert te == T
         if c == C - 1:
             assert tb == 0
+
+
+# ---- SyncBN: bn_world ranks against the big-batch plan, in every dtype and on every planned path of the BatchNorm counts
+
+
+@pytest.mark.parametrize("model,kn,ru,dtype,world,B,L,knob", [
+    ("DCCRN", SMALL["kernel_num"], 128, "bf16", 2, 4, 3000, None),               # the fused BatchNorm backward of enc0 (kRunDyFromBn) reads the count
+    ("DCCRN", SMALL["kernel_num"], 128, "bf16", 4, 4, 3000, None),               # one utterance per rank: a hard-coded 1/2 does not pass
+    ("DCCRN", SMALL["kernel_num"], 128, "bf16", 2, 4, 3000, ("ENC0_BNFUSE", "0")),  # unfused control arm: BN_BWD_APPLY carries the count
+    ("DCCRN", SMALL["kernel_num"], 128, "bf16", 2, 4, 3000, ("BN_FUSE", "2")),      # backward sums from the producers' epilogues (kRunBnBwd)
+    ("DCCRN", DEFAULT_KN, 256, "bf16", 2, 4, 2400, None),                        # default kernel_num: enc0 with N = 32
+    ("CRN", SMALL["kernel_num"], 128, "bf16", 2, 4, 3000, None),
+    ("DCCRN", SMALL["kernel_num"], 128, "fp32", 2, 4, 3000, None),
+])
+def test_syncbn_ranks_equal_big_batch_plan(model, kn, ru, dtype, world, B, L, knob):
+    """`world` bn_world plans over equal shards, statistics summed at every sync point, reproduce the bn_world = 1 plan over the whole
+    batch: outputs, gradients (ranks summed), BatchNorm running statistics."""
+    from simutil import syncbn_vs_big_batch
+    if knob:
+        knobs.set(*knob)
+    if model == "CRN":
+        from oracle.crn import CRNConfig, crn_state_shapes
+        P = formula_state_dict(crn_state_shapes(CRNConfig(kernel_num=kn, rnn_units=ru, rnn_input_size=4 * (kn[-1] // 2))))
+        mode = "E"
+    else:
+        mode = "C"
+        P = oracle_params(DCCRNConfig(masking_mode=mode, kernel_num=kn, rnn_units=ru))
+    P = unit_slopes(P)
+    x, y = make_signals(B, L)
+    torch.manual_seed(7)
+    inputs = {"wav": x} if model == "DCCRN" else {"wav": x, "tgt": y}
+
+    def make_plan(b, bn_world):
+        return Plan(b, L, masking_mode=mode, kernel_num=kn, rnn_units=ru, act_dtype=dtype, model=model, bn_world=bn_world)
+    res = syncbn_vs_big_batch(make_plan, P, inputs, {"grad_wav": torch.randn(B, L)}, world)
+    if model == "DCCRN" and dtype == "bf16":
+        # the plan under test must take the path it is meant to pin: if planning moves, fail here rather than pass on another path
+        plan = res["ranks"]["plans"][0]
+        fused = [i for i in range(plan.num_ops(PHASE_BWD)) if plan.op_info(PHASE_BWD, i)["kind"] == KIND_WGRAD and plan.op_info(PHASE_BWD, i)["tag"] == 100
+                 and plan.op_info(PHASE_BWD, i)["flags"] & RUN_DY_FROM_BN]
+        assert len(fused) == (0 if knob == ("ENC0_BNFUSE", "0") else 1), fused
+    errs = check_syncbn_result(res, dtype, only=DEFAULT_KN_ONLY if kn == DEFAULT_KN and dtype == "bf16" else None)
+    print(" ".join(f"{k} {v:.1e}" for k, v in sorted(errs.items(), key=lambda kv: -kv[1])[:6]))
+
+
+def test_enc0_descriptor_predicate_fires_on_a_misaligned_copy():
+    """sefd_desc.h enc0_accepts: the fused first-layer weight gradient of a real bf16 plan passes it; the same descriptor with an odd y_off
+    (which launch_enc0_wgrad declines - and no generic kernel reads kRunDyFromBn) fails it, so the host simulator would refuse to run it."""
+    from simutil import sim
+    plan = Plan(2, 3000, masking_mode="C", act_dtype="bf16", **SMALL)
+    sz = plan.lib.sefd_op_size()
+    idx = [i for i in range(plan.num_ops(PHASE_BWD)) if plan.op_info(PHASE_BWD, i)["kind"] == KIND_WGRAD and plan.op_info(PHASE_BWD, i)["tag"] == 100
+           and plan.op_info(PHASE_BWD, i)["flags"] & RUN_DY_FROM_BN]
+    assert len(idx) == 1, idx
+    op = plan.ops_ptr(PHASE_BWD) + idx[0] * sz
+    assert sim().hostsim_enc0_accepts(op, 0) == 1
+    assert sim().hostsim_enc0_accepts(op, 1) == 0
+    assert sim().hostsim_enc0_accepts(op, 8) == 1
