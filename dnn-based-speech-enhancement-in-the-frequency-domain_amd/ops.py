@@ -10,6 +10,7 @@ through ctypes (no dispatcher hop inside the fused train step); `tests/test_gpu_
                                                               differentiable w.r.t. est (rows of any length) and tgt (rows <= 16 elements)
     torch.ops.sefd.adam_step_(param, grad, m, v, step, ...)   torch.optim.Adam.step on flat fp32 buffers, in place
     torch.ops.sefd.mix_snr(speech, bank, start, snr_db, q)   generate_noisy_data.py:46-67 on the GPU
+    torch.ops.sefd.composite_measures(clean, enh, fs)         composite.m frame analysis: [B, 3] fp64 (trimmed LLR, trimmed WSS, segSNR)
     torch.ops.sefd.plan_run(handle, phase, arenas)            one phase (0 forward, 1 backward) of a planned model: sefd_plan_run
 """
 import ctypes as C
@@ -145,6 +146,20 @@ def mix_snr(speech: torch.Tensor, noise_bank: torch.Tensor, noise_start: torch.T
 @mix_snr.register_fake
 def _(speech, noise_bank, noise_start, snr_db, quantize):
     return torch.empty_like(speech, dtype=torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------- composite measure
+@torch.library.custom_op("sefd::composite_measures", mutates_args=())
+def composite_measures(clean: torch.Tensor, enhanced: torch.Tensor, fs: int) -> torch.Tensor:
+    """composite.m:56-75 frame analysis for a batch (sefd_composite_frames): clean / enhanced [B, L] -> fp64 [B, 3] = (95 % trimmed mean
+    LLR, 95 % trimmed mean WSS, mean segSNR) per utterance; tools_for_estimate.composite_batch adds PESQ and the regression."""
+    from .tools_for_estimate import composite_frames
+    return composite_frames(clean, enhanced, fs)
+
+
+@composite_measures.register_fake
+def _(clean, enhanced, fs):
+    return clean.new_empty((clean.shape[0], 3), dtype=torch.float64)
 
 
 # ---------------------------------------------------------------------------------------------- planned models

@@ -1,4 +1,4 @@
-"""`tools_for_estimate` under the reference's top-level module name (see dropin/models.py): cal_pesq / cal_stoi / cal_snr."""
+"""`tools_for_estimate` under the reference's top-level module name (see dropin/models.py): cal_pesq / cal_stoi / cal_snr, composite / pesq_mos."""
 import os
 import sys
 

@@ -177,6 +177,18 @@ int32_t sefd_pmsqe_backward(int32_t B, int32_t L, int32_t power, const float* ta
    flat fp32 bank, ws: 4 * B doubles.  All device pointers. */
 int32_t sefd_mix_snr(const float* speech, const float* noise, const int64_t* noise_start, const float* snr_db, int32_t B, int32_t L,
                      int32_t quantize, double* ws, float* noisy, void* stream);
+/* ---- Composite measure frame analysis (reference composite.m:151-562, called by tools_for_estimate.py:24-33) ------------------------------
+ * For a batch of clean / processed pairs (fp32 [B][L] device, same length): per 30 ms frame (win = round(30 fs / 1000), hop floor(win / 4),
+ * window 0.5 (1 - cos(2 pi n / (win + 1))), floor(L / hop - win / hop) frames, eps = 2^-52 added to every sample) the WSS distance
+ * (composite.m:151-384), the LLR (:385-491, LPC order 10 below 10 kHz, else 16) and the segmental SNR (:492-562); then per utterance
+ * out[b][0] = mean of the round(0.95 n) smallest LLRs, out[b][1] = the same of the WSS values, out[b][2] = mean segSNR (fp64 device [B][3]).
+ * No PESQ term and no [1, 5] clamp: the regression lives with the caller.  Bit-identical from run to run and independent of the rest of the
+ * batch.  ws: sefd_composite_ws_bytes(B, L, fs) bytes of device memory.  Returns 0, -1 bad arguments (B outside 1..65535, L < win, NULL),
+ * -2 launch failure, -3 more than SEFD_COMPOSITE_MAX_FRAMES frames per utterance, -4 fs whose n_fft = 2^nextpow2(2 win) is outside 256..4096
+ * (supported: about 4.3 to 68 kHz).  An utterance with L >= win but no whole frame (L < win + hop) gets NaN, the mean of nothing. */
+#define SEFD_COMPOSITE_MAX_FRAMES (1 << 24)
+int64_t sefd_composite_ws_bytes(int32_t B, int32_t L, int32_t fs);
+int32_t sefd_composite_frames(const float* clean, const float* enhanced, int32_t B, int32_t L, int32_t fs, void* ws, double* out, void* stream);
 int32_t sefd_fsn_targets(const float* noisy_c64, const float* clean_c64, int64_t n, float* mag, float* phase, float* cirm, void* stream);
 
 /* ---- Adam (torch.optim.Adam defaults, train_interface.py:59) on flat fp32 buffers ------------------
