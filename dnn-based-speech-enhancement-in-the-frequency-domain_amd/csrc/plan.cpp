@@ -42,6 +42,35 @@ static bool runs_aligned(const RunGemm& g, bool is_wgrad) {
   return ok;
 }
 
+// ConvSTFT / ConviSTFT window sample j (tools_for_model.py:17-20)
+static double window_value(const ModelConfig& cfg, int j, int W) {
+  if (cfg.window == 1) return 1.0;
+  if (cfg.window == 2 && cfg.window_values) return cfg.window_values[j];
+  return 0.5 - 0.5 * std::cos(2.0 * kPi * j / W);
+}
+
+// ConvSTFT / ConviSTFT front end of the DCCRN, CRN and front-end plans (tools_for_model.py:16-61): frame geometry, window, bases
+struct Stft {
+  int B = 0, L = 0, W = 0, hop = 0, NFFT = 0, trim = 0, T = 0, NF = 0, NS = 0, SW = 0, Lp = 0;
+  std::vector<double> win;
+  std::vector<double> Kinv;                                // synthesis basis [part][k][j] (Builder::synthesis)
+  Ptr c_coff = Ptr{-1, 0, 0};                              // OLA normaliser: sum of the squared windows over the frames covering a sample
+  Stft() = default;
+  explicit Stft(const ModelConfig& cfg) : B(cfg.B), L(cfg.L), W(cfg.win_len), hop(cfg.hop), NFFT(cfg.fft_len) {
+    trim = W - hop;
+    T = (L + 2 * trim - W) / hop + 1;
+    NF = NFFT / 2 + 1; NS = NF + 1; SW = NS * 2;             // spectrum rows: NS (re, im) pairs, slot 0 unused (aligned bins)
+    Lp = (T - 1) * hop + W;
+    win.resize(W);
+    for (int j = 0; j < W; ++j) win[j] = window_value(cfg, j, W);    // win_type None: np.ones (tools_for_model.py:17-18)
+  }
+  // analysis basis (tools_for_model.py:16-33): K[part*NF+k][j] = w[j]*{cos,-sin}(2 pi k j / NFFT), without the window
+  double Kun(int part, int k, int j) const {
+    const double ang = 2.0 * kPi * (double)(((int64_t)k * j) % NFFT) / NFFT;
+    return part == 0 ? std::cos(ang) : -std::sin(ang);
+  }
+};
+
 struct Builder {
   Plan* P;
   ModelConfig c;
@@ -225,6 +254,311 @@ struct Builder {
     return true;
   }
 
+  // ---- the ConvSTFT front end (fe) and its inverse
+  Stft fe;
+  Ptr ana_w = Ptr{-1, 0, 0};                               // analysis GEMM weights (shared by every STFT of the plan)
+  // synthesis basis = pinv(K_unwindowed)^T * w, closed form (SURVEY Q2): K^T K = (NFFT/2) I + E, E[n][m] = [n-m even]
+  //   pinv(K)[j][r] = (K[r][j] - sum_{m == j mod 2} K[r][m] / (NFFT/2 + |{m == j mod 2}|)) / (NFFT/2)
+  // and the OLA normaliser (constant c_coff)
+  void synthesis() {
+    const int W = fe.W, NF = fe.NF, NFFT = fe.NFFT;
+    fe.Kinv.assign((size_t)2 * NF * W, 0.0);
+    const double ne = (W + 1) / 2, no = W / 2;
+    for (int part = 0; part < 2; ++part)
+      for (int k = 0; k < NF; ++k) {
+        double se = 0, so = 0;
+        for (int m = 0; m < W; ++m) (m % 2 == 0 ? se : so) += fe.Kun(part, k, m);
+        for (int j = 0; j < W; ++j) {
+          const double corr = (j % 2 == 0) ? se / (NFFT / 2.0 + ne) : so / (NFFT / 2.0 + no);
+          fe.Kinv[((size_t)part * NF + k) * W + j] = (fe.Kun(part, k, j) - corr) / (NFFT / 2.0) * fe.win[j];
+        }
+      }
+    std::vector<float> coff(fe.Lp, 0.f), w2(W);
+    for (int j = 0; j < W; ++j) { const float wf = (float)fe.win[j]; w2[j] = wf * wf; }
+    for (int t = 0; t < fe.T; ++t)
+      for (int j = 0; j < W; ++j) coff[t * fe.hop + j] += w2[j];
+    fe.c_coff = cst(coff.data(), (int64_t)coff.size() * 4);
+  }
+  // constant (fp32) weights of a single-run GEMM: w[n][j] = val(n, j)
+  void const_weights(RunGemm& g, const std::function<double(int n, int j)>& val) {
+    std::vector<float> wt((size_t)g.Npad * g.ldw, 0.f);
+    for (int nn = 0; nn < g.N; ++nn)
+      for (int j = 0; j < g.seg[0].len; ++j) wt[(size_t)nn * g.ldw + j] = (float)val(nn, j);
+    g.w = cst(wt.data(), (int64_t)wt.size() * 4);
+  }
+  // STFT (ConvSTFT.forward, tools_for_model.py:54-61) wav [B][L] -> spec [B*T][SW]: the fused FFT, else the framing GEMM.  True: FFT
+  bool stft_fwd(std::vector<Op>& ops, int tag, Ptr wav, Ptr spec) {
+    if (stft_fft(ops, tag, wav, spec, fe.B, fe.L, fe.T, fe.hop, fe.trim, fe.NFFT, fe.win)) return true;
+    RunGemm g = gemm0();
+    g.x[0] = wav; g.xdt = DT_F32; g.ydt = DT_F32;
+    g.bstride[0] = fe.L; g.rowlen[0] = fe.L; g.fstride[0] = fe.hop; g.Tin[0] = 1;
+    g.M = fe.B * fe.T; g.Tout = 1; g.Fo = fe.T;
+    g.nseg = 1; g.seg[0] = Seg{0, 0, -fe.trim, fe.W, 0};
+    g.N = fe.SW;
+    layout_segs(g);
+    if (ana_w.arena < 0) {
+      const_weights(g, [&](int nn, int j) { return nn < 2 ? 0.0 : fe.Kun(nn & 1, nn / 2 - 1, j) * fe.win[j]; });
+      ana_w = g.w;
+    }
+    g.w = ana_w;
+    g.y = spec; g.y_bstride = (int64_t)fe.T * fe.SW; g.y_fstride = fe.SW;
+    push(ops, OP_RUNGEMM, tag).g = g;
+    return false;
+  }
+  // iSTFT (ConviSTFT.forward) est [B*T][SW] -> frames [B*T][W] (inverse FFT, else the synthesis GEMM), then the overlap-add into wav
+  Ola istft_ola(std::vector<Op>& ops, Ptr est, Ptr frames, Ptr wav) {
+    const int64_t BT = (int64_t)fe.B * fe.T;
+    if (!istft_fft(ops, 501, est, frames, BT, fe.NFFT, fe.win)) {
+      RunGemm g = gemm0();
+      g.x[0] = est; g.xdt = DT_F32; g.ydt = DT_F32;
+      g.bstride[0] = (int64_t)fe.T * fe.SW; g.tstride[0] = fe.SW; g.rowlen[0] = fe.SW; g.Tin[0] = fe.T;
+      g.M = (int)BT; g.Tout = fe.T; g.Fo = 1;
+      g.nseg = 1; g.seg[0] = Seg{0, 0, 0, fe.SW, 0};
+      g.N = fe.W;
+      layout_segs(g);
+      const int NF = fe.NF, W = fe.W;
+      const_weights(g, [&](int nn, int j) { return j < 2 ? 0.0 : fe.Kinv[((size_t)(j & 1) * NF + (j / 2 - 1)) * W + nn]; });
+      g.y = frames; g.y_bstride = (int64_t)fe.T * W; g.y_tstride = W;
+      push(ops, OP_RUNGEMM, 501).g = g;
+    }
+    Ola ola;
+    std::memset(&ola, 0, sizeof(ola));
+    ola.frames = frames; ola.wav = wav; ola.coff = fe.c_coff; ola.dwav = ola.dpad = none();
+    ola.B = fe.B; ola.T = fe.T; ola.L = fe.L; ola.win = fe.W; ola.hop = fe.hop; ola.trim = fe.trim;
+    push(ops, OP_OLA_FWD, 502).ola = ola;
+    return ola;
+  }
+  // their backward: the overlap-add's (dwav -> dpad), then the iSTFT's (dpad -> the returned dest [B*T][SW])
+  Ptr istft_ola_bwd(std::vector<Op>& ops, const Ola& ola, Ptr dwav) {
+    const int64_t BT = (int64_t)fe.B * fe.T;
+    Ptr dpad = ws("dpad", (int64_t)fe.B * fe.Lp, DT_F32);
+    Ptr dest = ws("dest", BT * fe.SW, DT_F32);
+    Ola o = ola;
+    o.dwav = dwav; o.dpad = dpad;
+    push(ops, OP_OLA_BWD, 502).ola = o;
+    if (!istft_bwd_fft(ops, 501, dpad, dest, fe.B, fe.Lp, fe.T, fe.hop, fe.NFFT, fe.win)) {
+      RunGemm g = gemm0();
+      g.x[0] = dpad; g.xdt = DT_F32; g.ydt = DT_F32;
+      g.bstride[0] = fe.Lp; g.rowlen[0] = fe.Lp; g.fstride[0] = fe.hop; g.Tin[0] = 1;
+      g.M = (int)BT; g.Tout = 1; g.Fo = fe.T;
+      g.nseg = 1; g.seg[0] = Seg{0, 0, 0, fe.W, 0};
+      g.N = fe.SW;
+      layout_segs(g);
+      const int NF = fe.NF, W = fe.W;
+      const_weights(g, [&](int nn, int j) { return nn < 2 ? 0.0 : fe.Kinv[((size_t)(nn & 1) * NF + (nn / 2 - 1)) * W + j]; });
+      g.y = dest; g.y_bstride = (int64_t)fe.T * fe.SW; g.y_fstride = fe.SW;
+      push(ops, OP_RUNGEMM, 501).g = g;
+    }
+    return dest;
+  }
+
+  // ---- the conv stack shared by the DCCRN (complex convs as block-real GEMMs) and CRN (real convs) planners
+  using Bias = std::function<void(int n, int32_t out[2])>;
+  struct ActSrc { Ptr p; int64_t bstride; int tstride, base, C; };      // channels-last activation: batch / frame strides, first element, channels
+  // one conv layer: forward descriptor(s) (decoder: one per sub-pixel phase) with their coefficient and bias functions, activations
+  // (y conv output, z BatchNorm + PReLU output, mi its statistics), C channels, Fq frequency bins, R BatchNorm rows; gradient buffers
+  struct ConvLayer { RunGemm f[2]; Coef coef[2]; Bias bias; Ptr y, z, mi, dy, dz, dskip; int C, Fq; int64_t R; };
+
+  // BatchNorm2d + PReLU forward of a conv layer (parameters <pp>.1 / <pp>.2): y -> z.  Training: batch statistics from nblk partial rows
+  // of pitch Cpad in `part` (nsub > 0: each row holds nsub sub-pixel phases substride columns apart)
+  void bn_fwd(std::vector<Op>& ops, int tag, const std::string& pp, const ConvLayer& Ly, Ptr part, int nblk, int Cpad, int nsub, int substride) {
+    Op& op = push(ops, OP_BN_FINALIZE, tag);
+    op.bnf.part = part; op.bnf.mean_invstd = Ly.mi;
+    op.bnf.running_mean = sptr(pp + ".1.running_mean"); op.bnf.running_var = sptr(pp + ".1.running_var");
+    op.bnf.nblk = c.training ? nblk : -1; op.bnf.C = Ly.C; op.bnf.Cpad = Cpad; op.bnf.count = (double)Ly.R;
+    op.bnf.nsub = nsub; op.bnf.substride = substride;
+    op.bnf.eps = 1e-5f; op.bnf.momentum = 0.1f;
+    Op& oa = push(ops, OP_BN_APPLY, tag);
+    oa.bna.y = Ly.y; oa.bna.z = Ly.z; oa.bna.mean_invstd = Ly.mi;
+    oa.bna.gamma = pptr(pp + ".1.weight"); oa.bna.beta = pptr(pp + ".1.bias"); oa.bna.slope = pptr(pp + ".2.weight");
+    oa.bna.R = Ly.R; oa.bna.C = Ly.C; oa.bna.dt = c.act_dtype;
+  }
+  // Encoder conv (kernel KS x 2 over (frequency, time), frequency stride 2, frames t-1 and t) over the channels-last input x (coef / bias
+  // map its channels to parameters, zero for pad channels): packed weights, RUNGEMM into <nm>.y, then with `bn` BatchNorm + PReLU into
+  // <nm>.z.  enc0: DCCRN's first layer reading the fp32 spectrum itself (kRunEnc0, enc0.hip)
+  ConvLayer enc_conv(std::vector<Op>& ops, int tag, const std::string& nm, const std::string& pp, const ActSrc& x, int Fi, int Fo, int Co,
+                     const Coef& coef, const Bias& bias, bool bn, bool enc0) {
+    const int adt = c.act_dtype, KS = c.kernel_size, T = fe.T;
+    ConvLayer Ly{};
+    RunGemm g = gemm0();
+    g.x[0] = x.p;
+    g.xdt = enc0 ? DT_F32 : adt;
+    g.ydt = adt;
+    if (enc0) g.flags |= kRunEnc0;
+    g.bstride[0] = x.bstride; g.tstride[0] = x.tstride; g.base[0] = x.base;
+    g.rowlen[0] = Fi * x.C; g.fstride[0] = 2 * x.C; g.Tin[0] = T;
+    g.M = fe.B * T * Fo; g.Tout = T; g.Fo = Fo;
+    g.nseg = 2;
+    g.seg[0] = Seg{0, -1, -2 * x.C, KS * x.C, 0};   // kw = 0 : frame t-1
+    g.seg[1] = Seg{0, 0, -2 * x.C, KS * x.C, 0};    // kw = 1 : frame t
+    g.N = Co;
+    layout_segs(g);
+    pack_weights(ops, g, coef, nm, tag, &bias);
+    Ly.C = Co; Ly.Fq = Fo; Ly.R = (int64_t)fe.B * T * Fo;
+    Ly.y = ws(nm + ".y", Ly.R * Co, adt);
+    Ly.z = ws(nm + ".z", Ly.R * Co, adt);
+    Ly.mi = ws(nm + ".mi", 2 * Co, DT_F32);
+    const int nblk = (int)((g.M + kBM - 1) / kBM);
+    Ptr part = ws(nm + ".stat", (int64_t)nblk * 2 * g.Npad, DT_F32);
+    g.y = Ly.y; g.y_bstride = (int64_t)T * Fo * Co; g.y_tstride = Fo * Co; g.y_fstride = Co; g.y_off = 0;
+    g.stats = c.training && bn ? part : none();
+    push(ops, OP_RUNGEMM, tag).g = g;
+    if (bn) bn_fwd(ops, tag, pp, Ly, part, nblk, g.Npad, 0, 0);
+    Ly.f[0] = g; Ly.coef[0] = coef; Ly.bias = bias;
+    return Ly;
+  }
+  // Decoder transposed conv (kernel KS x 2, frequency stride 2; Ly.y keeps the extra frame that `[..., 1:]` drops) as two sub-pixel phase
+  // GEMMs over src[0] (previous layer) and, with skips, src[1]: phase 0 = output bins 2f (taps kh = 4, 2, 0 over input bins f-1, f, f+1),
+  // phase 1 = bins 2f+1 (kh = 3, 1 over bins f, f+1).  wcoef(n, source, channel, kh, kw); N output columns ([phase][N] per input bin);
+  // stats: BatchNorm partial rows, nblk1 per phase (none: no statistics).  pack = false: descriptors and coefficients only
+  using WCoef = std::function<int32_t(int n, int s, int cc, int kh, int kw)>;
+  void dec_phases(std::vector<Op>& ops, int tag, const std::string& nm, ConvLayer& Ly, const std::array<ActSrc, 2>& src, int Fi, int N,
+                  const WCoef& wcoef, Ptr stats, int nblk1, bool pack) {
+    const int adt = c.act_dtype, T = fe.T, Fo = 2 * Fi, nsrc = c.skip ? 2 : 1;
+    for (int par = 0; par < 2; ++par) {
+      RunGemm g = gemm0();
+      g.xdt = adt; g.ydt = adt;
+      g.nseg = 0;
+      const int ntap = par == 0 ? 3 : 2;
+      for (int s = 0; s < nsrc; ++s) {
+        g.x[s] = src[s].p; g.bstride[s] = src[s].bstride; g.tstride[s] = src[s].tstride; g.base[s] = src[s].base;
+        g.rowlen[s] = Fi * src[s].C; g.fstride[s] = src[s].C; g.Tin[s] = T;
+        for (int kw = 0; kw < 2; ++kw) g.seg[g.nseg++] = Seg{s, -kw, par == 0 ? -src[s].C : 0, ntap * src[s].C, 0};
+      }
+      g.M = fe.B * (T + 1) * Fi; g.Tout = T + 1; g.Fo = Fi;
+      g.N = N;
+      layout_segs(g);
+      const int c0 = src[0].C, c1 = src[1].C;
+      Coef coef = [=](int nn, int sg, int j) -> int32_t {
+        const int s = sg / 2, kw = sg % 2;
+        const int Cs = s == 0 ? c0 : c1;
+        const int jj = j / Cs, cc = j % Cs;
+        return wcoef(nn, s, cc, par == 0 ? 4 - 2 * jj : 3 - 2 * jj, kw);
+      };
+      Ly.coef[par] = coef;
+      if (!pack) { Ly.f[par] = g; continue; }
+      pack_weights(ops, g, coef, nm + ".p" + std::to_string(par), tag, par == 0 ? &Ly.bias : nullptr);
+      if (par == 1) g.bias = Ly.f[0].bias;
+      g.y = Ly.y; g.y_bstride = (int64_t)(T + 1) * Fo * N; g.y_tstride = Fo * N; g.y_fstride = 2 * N; g.y_off = par * N;
+      if (stats.arena >= 0) g.stats = mk(A_WS, stats.off + (int64_t)par * nblk1 * 2 * g.Npad * 4);
+      push(ops, OP_RUNGEMM, tag).g = g;
+      Ly.f[par] = g;
+    }
+  }
+  // gradient buffers of the conv stack (the mask layer's dy has mask_ch channels)
+  void conv_grads(std::vector<ConvLayer>& enc, std::vector<ConvLayer>& dec, int mask_ch) {
+    const int n = (int)enc.size(), adt = c.act_dtype, B = fe.B, T = fe.T;
+    for (int d = 0; d < n; ++d) {
+      const int Co = d == n - 1 ? mask_ch : dec[d].C, Fo = dec[d].Fq;
+      dec[d].dy = ws("dec" + std::to_string(d) + ".dy", (int64_t)B * (T + 1) * Fo * Co, adt);
+      if (d != n - 1) dec[d].dz = ws("dec" + std::to_string(d) + ".dz", (int64_t)B * T * Fo * Co, adt);
+    }
+    for (int i = 0; i < n; ++i) {
+      const int64_t e = (int64_t)B * T * enc[i].Fq * enc[i].C;
+      enc[i].dy = ws("enc" + std::to_string(i) + ".dy", e, adt);
+      enc[i].dz = ws("enc" + std::to_string(i) + ".dz", e, adt);
+      if (c.skip) enc[i].dskip = ws("enc" + std::to_string(i) + ".dskip", e, adt);
+    }
+  }
+  // DCCRN: BatchNorm backward partial rows left by the epilogues of the GEMMs that produce a layer's dz (kRunBnBwd)
+  struct BnbAcc { Ptr part; int rows = 0, cap = 0, ldp = 0; bool on = false; Ptr y, mi; std::string pp; };
+  // BatchNorm2d + PReLU backward of a conv layer: dz0 (+ dz1, the skip connection's) -> dy and the parameter gradients; rpb rows per
+  // batch item, the first `skip` of them not in dz.  DCCRN only: cbn = ComplexBatchNorm (mi = its coefficient table), fused = the
+  // producers' epilogues wrote the partial rows, no_apply = no BN_BWD_APPLY.  Returns the BN_BWD_FINALIZE descriptor.
+  BnBwdApply bn_bwd(std::vector<Op>& R, int tag, Ptr y, Ptr dz0, Ptr dz1, Ptr mi, const std::string& pp, int C, int64_t Rr, int64_t rpb,
+                    int skip, Ptr dy, const std::string& nm, bool cbn, const BnbAcc* fused, bool no_apply) {
+    const int adt = c.act_dtype;
+    int64_t rpbk = std::max<int64_t>(64, (Rr + 2047) / 2048);
+    const int nblk = (int)((Rr + rpbk - 1) / rpbk);
+    BnBwdApply a;
+    std::memset(&a, 0, sizeof(a));
+    if (cbn) {
+      const int h = C / 2;
+      CbnBwd cb;
+      std::memset(&cb, 0, sizeof(cb));
+      cb.y = y; cb.dz0 = dz0; cb.dz1 = dz1; cb.dy = dy; cb.coef = mi;
+      cb.coefb = ws(nm + ".ccoefb", 9 * h, DT_F32);
+      cb.part = ws(nm + ".cbnpart", (int64_t)nblk * 7 * h, DT_F32);
+      const char* wn[3] = {"Wrr", "Wri", "Wii"};
+      for (int q = 0; q < 3; ++q) { cb.W[q] = pptr(pp + ".1." + wn[q]); cb.dW[q] = pptr(pp + ".1." + wn[q], A_GRAD); }
+      cb.dB[0] = pptr(pp + ".1.Br", A_GRAD); cb.dB[1] = pptr(pp + ".1.Bi", A_GRAD);
+      cb.slope = pptr(pp + ".2.weight"); cb.dslope = pptr(pp + ".2.weight", A_GRAD);
+      cb.R = Rr; cb.rpb = rpb; cb.C = C; cb.dt = adt; cb.nblk = nblk; cb.rows_per_blk = (int)rpbk; cb.skip = skip; cb.count = (double)Rr;
+      push(R, OP_CBN_BWD_REDUCE, tag).cbb = cb;
+      push(R, OP_CBN_BWD_FINALIZE, tag).cbb = cb;
+      push(R, OP_CBN_BWD_APPLY, tag).cbb = cb;
+      return a;
+    }
+    BnBwdReduce r;
+    std::memset(&r, 0, sizeof(r));
+    r.y = y; r.dz0 = dz0; r.dz1 = dz1; r.mean_invstd = mi;
+    r.gamma = pptr(pp + ".1.weight"); r.beta = pptr(pp + ".1.bias"); r.slope = pptr(pp + ".2.weight");
+    r.R = Rr; r.C = C; r.dt = adt; r.nblk = nblk; r.rows_per_blk = (int)rpbk; r.rpb = rpb; r.skip = skip;
+    if (fused && fused->on) {                   // the producers' epilogues wrote the partial rows
+      r.part = fused->part; r.nblk = fused->rows; r.ldp = fused->ldp;
+    } else {
+      r.part = ws(nm + ".bnpart", (int64_t)nblk * 3 * C, DT_F32);
+      push(R, OP_BN_BWD_REDUCE, tag).bnr = r;
+    }
+    a.r = r; a.totals = ws(nm + ".bntot", 3 * C, DT_F32); a.dy = dy;
+    a.dgamma = pptr(pp + ".1.weight", A_GRAD); a.dbeta = pptr(pp + ".1.bias", A_GRAD); a.dslope = pptr(pp + ".2.weight", A_GRAD);
+    a.count = (double)Rr;
+    push(R, OP_BN_BWD_FINALIZE, tag).bnb = a;
+    if (!no_apply) push(R, OP_BN_BWD_APPLY, tag).bnb = a;
+    return a;
+  }
+  // Input gradient of decoder source s (Cs channels) as a conv over Ly.dy [B][T+1][Fo][Co] (Co: its buffer channels), read off the
+  // forward phases' coefficients: dx[ci,f,t] = sum W[ci,co,kh,kw] dy[co, 2f+kh-2, t+kw] into dx [B][T][Fi][Cs].  Packed unless `pack` is
+  // false; not pushed
+  RunGemm dec_dgrad(std::vector<Op>& ops, int tag, const std::string& nm, const ConvLayer& Ly, int Co, int Fi, int s, int Cs, Ptr dx,
+                    Coef& coef, bool pack) {
+    const int adt = c.act_dtype, KS = c.kernel_size, T = fe.T, Fo = 2 * Fi;
+    RunGemm g = gemm0();
+    g.x[0] = Ly.dy; g.xdt = adt; g.ydt = adt;
+    g.bstride[0] = (int64_t)(T + 1) * Fo * Co; g.tstride[0] = Fo * Co; g.base[0] = 0; g.rowlen[0] = Fo * Co; g.fstride[0] = 2 * Co; g.Tin[0] = T + 1;
+    g.M = fe.B * T * Fi; g.Tout = T; g.Fo = Fi;
+    g.nseg = 2;
+    g.seg[0] = Seg{0, 0, -2 * Co, KS * Co, 0};    // kw = 0 : buffer frame u = t
+    g.seg[1] = Seg{0, 1, -2 * Co, KS * Co, 0};    // kw = 1 : buffer frame u = t + 1
+    g.N = Cs;
+    layout_segs(g);
+    // d y[co] / d x[(s,cc)] is the forward coefficient of phase (kh odd) at tap jj: look it up in the forward tables
+    const Coef f0 = Ly.coef[0], f1 = Ly.coef[1];
+    coef = [=](int nn, int sg, int j) -> int32_t {
+      const int kw = sg, kh = j / Co, co = j % Co;
+      const int par = kh & 1;
+      const int jj = par == 0 ? (4 - kh) / 2 : (3 - kh) / 2;
+      return (par == 0 ? f0 : f1)(co, s * 2 + kw, jj * Cs + nn);
+    };
+    if (pack) pack_weights(ops, g, coef, nm + ".dg" + std::to_string(s), tag);
+    g.y = dx; g.y_bstride = (int64_t)T * Fi * Cs; g.y_tstride = Fi * Cs; g.y_fstride = Cs; g.y_off = 0;
+    return g;
+  }
+  // Input gradient of encoder layer Ly (Ci input channels, Fi input bins): dx[ci,f,t] = sum W[co,ci,kh,kw] dy[co,(f+2-kh)/2, t+1-kw] as
+  // sub-pixel phase `par` over Ly.dy [B][T][Fo][Co], writing bins 2f+par of dx [B][T][Fi][Ci].  Packed, not pushed
+  RunGemm enc_dgrad(std::vector<Op>& ops, int tag, const std::string& nm, const ConvLayer& Ly, int Ci, int Fi, int par, Ptr dx) {
+    const int adt = c.act_dtype, T = fe.T, Co = Ly.C, Fo = Ly.Fq;
+    RunGemm g = gemm0();
+    g.x[0] = Ly.dy; g.xdt = adt; g.ydt = adt;
+    g.bstride[0] = (int64_t)T * Fo * Co; g.tstride[0] = Fo * Co; g.rowlen[0] = Fo * Co; g.fstride[0] = Co; g.Tin[0] = T;
+    g.M = fe.B * T * Fo; g.Tout = T; g.Fo = Fo;           // Fi/2 == Fo output rows per phase
+    const int ntap = par == 0 ? 3 : 2;
+    g.nseg = 2;
+    g.seg[0] = Seg{0, 1, par == 0 ? -Co : 0, ntap * Co, 0};   // kw = 0 : frame t+1
+    g.seg[1] = Seg{0, 0, par == 0 ? -Co : 0, ntap * Co, 0};   // kw = 1 : frame t
+    g.N = Ci;
+    layout_segs(g);
+    const Coef cf = Ly.coef[0];
+    Coef coef = [=](int nn, int sg, int j) -> int32_t {
+      const int kw = sg, jj = j / Co, co = j % Co;
+      const int kh = par == 0 ? 4 - 2 * jj : 3 - 2 * jj;
+      return cf(co, kw, kh * Ci + nn);
+    };
+    pack_weights(ops, g, coef, nm + ".dg" + std::to_string(par), tag);
+    g.y = dx; g.y_bstride = (int64_t)T * Fi * Ci; g.y_tstride = Fi * Ci; g.y_fstride = 2 * Ci; g.y_off = par * Ci;
+    return g;
+  }
+
   // WGRAD for the layer whose forward descriptor is `f` (same A runs + a ones run) against upstream gradient `dy`.
   void wgrad(std::vector<Op>& ops, const RunGemm& f, Ptr dy, const Coef& coef, int tag,
              const std::function<void(int n, int32_t out[2])>* bias) {
@@ -385,14 +719,6 @@ struct Builder {
     }
   }
 };
-
-// ConvSTFT / ConviSTFT window sample j (tools_for_model.py:17-20)
-static double window_value(const ModelConfig& cfg, int j, int W) {
-  const double kPi_ = 3.14159265358979323846;
-  if (cfg.window == 1) return 1.0;
-  if (cfg.window == 2 && cfg.window_values) return cfg.window_values[j];
-  return 0.5 - 0.5 * std::cos(2.0 * kPi_ * j / W);
-}
 
 int32_t pe(const ParamInfo& p, int64_t idx, int sign = 1) { return (int32_t)(sign * (p.off + idx + 1)); }
 
@@ -566,6 +892,17 @@ void finalize_rungemms(Builder& b, Plan* P) {
   }
 }
 
+// Plan epilogue: the post-pass, then the arena sizes (nparam trainable elements, nstate BatchNorm buffer elements; at least one each)
+void finish_plan(Builder& b, Plan* P, int64_t nparam, int64_t nstate) {
+  finalize_rungemms(b, P);
+  P->arena_bytes[A_WS] = b.ws_off;
+  P->arena_bytes[A_PARAM] = std::max<int64_t>(nparam, 1) * 4;
+  P->arena_bytes[A_GRAD] = std::max<int64_t>(nparam, 1) * 4;
+  P->arena_bytes[A_STATE] = std::max<int64_t>(nstate, 1) * 4;
+  P->arena_bytes[A_CONST] = (int64_t)P->consts.size();
+  P->arena_bytes[A_IO] = b.io_off;
+}
+
 }  // namespace
 
 // =================================================================================================================
@@ -575,12 +912,9 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
   Builder b;
   b.P = P;
   b.c = cfg;
+  b.fe = Stft(cfg);
   const int n = cfg.n_layers;
-  const int B = cfg.B, L = cfg.L, W = cfg.win_len, hop = cfg.hop, NFFT = cfg.fft_len;
-  const int trim = W - hop;
-  const int T = (L + 2 * trim - W) / hop + 1;
-  const int NF = NFFT / 2 + 1, NS = NF + 1, SW = NS * 2;
-  const int Lp = (T - 1) * hop + W;
+  const int B = cfg.B, L = cfg.L, W = cfg.win_len, T = b.fe.T, NF = b.fe.NF, NS = b.fe.NS, SW = b.fe.SW;
   const int adt = cfg.act_dtype;
   const int KS = cfg.kernel_size;
   P->T = T;
@@ -707,44 +1041,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
   Ptr io_gr = b.io("grad_real", (int64_t)B * NF * T);
   Ptr io_gi = b.io("grad_imag", (int64_t)B * NF * T);
 
-  // ------------------------------------------------------------------ constants: STFT bases, OLA normaliser
-  // analysis basis (tools_for_model.py:16-33): K[part*NF+k][j] = w[j]*{cos,-sin}(2 pi k j / NFFT); periodic Hann
-  std::vector<double> win(W);
-  for (int j = 0; j < W; ++j) win[j] = window_value(cfg, j, W);    // win_type None: np.ones (tools_for_model.py:17-18)
-  auto Kun = [&](int part, int k, int j) {
-    const double ang = 2.0 * kPi * (double)(((int64_t)k * j) % NFFT) / NFFT;
-    return part == 0 ? std::cos(ang) : -std::sin(ang);
-  };
-  // synthesis basis = pinv(K_unwindowed)^T * w, closed form (SURVEY Q2): K^T K = (NFFT/2) I + E, E[n][m] = [n-m even]
-  //   pinv(K)[j][r] = (K[r][j] - sum_{m == j mod 2} K[r][m] / (NFFT/2 + |{m == j mod 2}|)) / (NFFT/2)
-  std::vector<double> Kinv((size_t)2 * NF * W);
-  {
-    const double ne = (W + 1) / 2, no = W / 2;
-    for (int part = 0; part < 2; ++part)
-      for (int k = 0; k < NF; ++k) {
-        double se = 0, so = 0;
-        for (int m = 0; m < W; ++m) (m % 2 == 0 ? se : so) += Kun(part, k, m);
-        for (int j = 0; j < W; ++j) {
-          const double corr = (j % 2 == 0) ? se / (NFFT / 2.0 + ne) : so / (NFFT / 2.0 + no);
-          Kinv[((size_t)part * NF + k) * W + j] = (Kun(part, k, j) - corr) / (NFFT / 2.0) * win[j];
-        }
-      }
-  }
-  std::vector<float> coff(Lp, 0.f);
-  {
-    std::vector<float> w2(W);
-    for (int j = 0; j < W; ++j) { const float wf = (float)win[j]; w2[j] = wf * wf; }
-    for (int t = 0; t < T; ++t)
-      for (int j = 0; j < W; ++j) coff[t * hop + j] += w2[j];
-  }
-  Ptr c_coff = b.cst(coff.data(), (int64_t)coff.size() * 4);
-
-  auto const_weights = [&](RunGemm& g, const std::function<double(int n, int j)>& val) {
-    std::vector<float> wt((size_t)g.Npad * g.ldw, 0.f);
-    for (int nn = 0; nn < g.N; ++nn)
-      for (int j = 0; j < g.seg[0].len; ++j) wt[(size_t)nn * g.ldw + j] = (float)val(nn, j);
-    g.w = b.cst(wt.data(), (int64_t)wt.size() * 4);
-  };
+  b.synthesis();
 
   std::vector<Op>& F = P->fwd;
   std::vector<Op>& R = P->bwd;
@@ -752,19 +1049,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
   // ------------------------------------------------------------------ STFT (ConvSTFT.forward, tools_for_model.py:54-61)
   Ptr spec = b.ws("spec", (int64_t)B * T * SW, DT_F32);
   Ptr spec_lp = spec;
-  const bool spec_fft = b.stft_fft(F, 1, io_wav, spec, B, L, T, hop, trim, NFFT, win);
-  if (!spec_fft) {
-    RunGemm g = Builder::gemm0();
-    g.x[0] = io_wav; g.xdt = DT_F32; g.ydt = DT_F32;
-    g.bstride[0] = L; g.tstride[0] = 0; g.base[0] = 0; g.rowlen[0] = L; g.fstride[0] = hop; g.Tin[0] = 1;
-    g.M = B * T; g.Tout = 1; g.Fo = T;
-    g.nseg = 1; g.seg[0] = Seg{0, 0, -trim, W, 0};
-    g.N = SW;
-    Builder::layout_segs(g);
-    const_weights(g, [&](int nn, int j) { return nn < 2 ? 0.0 : Kun(nn & 1, nn / 2 - 1, j) * win[j]; });
-    g.y = spec; g.y_bstride = (int64_t)T * SW; g.y_tstride = 0; g.y_fstride = SW; g.y_off = 0;
-    b.push(F, OP_RUNGEMM, 1).g = g;
-  }
+  const bool spec_fft = b.stft_fwd(F, 1, io_wav, spec);
   // encoder input: spectrogram with the 2 channels padded to CP (aligned 16-byte runs for the thin first layer), act dtype
   const int CP = 8;
   // bf16 plans (round 6): the first layer reads the fp32 spectrum itself - no padded copy (64 MB written and read per step at B = 32), K = 20 instead of
@@ -783,32 +1068,15 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
   }
 
   // ------------------------------------------------------------------ encoder
-  struct Layer { RunGemm f[2]; Builder::Coef coef[2]; std::function<void(int, int32_t*)> bias; bool has_bias_fn; Ptr y, z, mi; int C, Fq; int64_t R; };
-  std::vector<Layer> enc(n), dec(n);
-  std::vector<Ptr> encz(n), ency(n), enc_mi(n);
-  Ptr prev = enc0_direct ? spec : spec_lp;
+  std::vector<Builder::ConvLayer> enc(n), dec(n);
+  const int C0b = enc0_direct ? 2 : CP;            // channels of the first layer's input BUFFER (padded, or the spectrum's (re, im) pairs)
+  Builder::ActSrc x{enc0_direct ? spec : spec_lp, (int64_t)T * NS * C0b, NS * C0b, 2 * C0b, C0b};
   for (int i = 0; i < n; ++i) {
-    const int Ci = ch[i], Co = ch[i + 1], Fi = Fe[i], Fo = Fe[i + 1];
-    const bool direct0 = i == 0 && enc0_direct;
-    const int Cib = i == 0 ? (direct0 ? 2 : CP) : Ci;             // channels of the input BUFFER (first layer: padded, or the spectrum's (re, im) pairs)
+    const int Ci = ch[i], Co = ch[i + 1], Fo = Fe[i + 1], Cib = x.C;
     const std::string nm = "enc" + std::to_string(i);
     const std::string pp = "encoder." + std::to_string(i);
     const ParamInfo &Wr = b.par(pp + ".0.real_conv.weight"), &Wi = b.par(pp + ".0.imag_conv.weight");
     const ParamInfo &br = b.par(pp + ".0.real_conv.bias"), &bi = b.par(pp + ".0.imag_conv.bias");
-    RunGemm g = Builder::gemm0();
-    g.x[0] = prev;
-    g.xdt = direct0 ? DT_F32 : adt;
-    g.ydt = adt;
-    if (direct0) g.flags |= kRunEnc0;
-    if (i == 0) { g.bstride[0] = (int64_t)T * NS * Cib; g.tstride[0] = NS * Cib; g.base[0] = 2 * Cib; }
-    else { g.bstride[0] = (int64_t)T * Fi * Ci; g.tstride[0] = Fi * Ci; g.base[0] = 0; }
-    g.rowlen[0] = Fi * Cib; g.fstride[0] = 2 * Cib; g.Tin[0] = T;
-    g.M = B * T * Fo; g.Tout = T; g.Fo = Fo;
-    g.nseg = 2;
-    g.seg[0] = Seg{0, -1, -2 * Cib, KS * Cib, 0};   // kw = 0 : frame t-1
-    g.seg[1] = Seg{0, 0, -2 * Cib, KS * Cib, 0};    // kw = 1 : frame t
-    g.N = Co;
-    Builder::layout_segs(g);
     const int Ci2 = Ci / 2, Co2 = Co / 2;
     Builder::Coef coef = [=](int nn, int s, int j) -> int32_t {
       const int kw = s, kh = j / Cib, ci = j % Cib;
@@ -819,45 +1087,23 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       if (!oi) return ii ? pe(Wi, idx, -1) : pe(Wr, idx, 1);
       return ii ? pe(Wr, idx, 1) : pe(Wi, idx, 1);
     };
-    std::function<void(int, int32_t*)> bias = [=](int nn, int32_t* o) {
+    Builder::Bias bias = [=](int nn, int32_t* o) {
       if (nn < Co2) { o[0] = pe(br, nn, 1); o[1] = pe(bi, nn, -1); }
       else { o[0] = pe(br, nn - Co2, 1); o[1] = pe(bi, nn - Co2, 1); }
     };
-    b.pack_weights(F, g, coef, nm, 100 + i, &bias);
-    const int64_t Rr = (int64_t)B * T * Fo;
-    ency[i] = b.ws(nm + ".y", Rr * Co, adt);
-    encz[i] = b.ws(nm + ".z", Rr * Co, adt);
-    enc_mi[i] = b.ws(nm + ".mi", 2 * Co, DT_F32);
-    const int nblk = (int)((g.M + kBM - 1) / kBM);
-    Ptr part = b.ws(nm + ".stat", (int64_t)nblk * 2 * g.Npad, DT_F32);
-    g.y = ency[i]; g.y_bstride = (int64_t)T * Fo * Co; g.y_tstride = Fo * Co; g.y_fstride = Co; g.y_off = 0;
-    g.stats = cfg.training && !cbn ? part : b.none();
-    b.push(F, OP_RUNGEMM, 100 + i).g = g;
+    enc[i] = b.enc_conv(F, 100 + i, nm, pp, x, Fe[i], Fo, Co, coef, bias, !cbn, i == 0 && enc0_direct);
     if (cbn) {
-      enc_mi[i] = cbn_fwd(100 + i, pp, nm, ency[i], encz[i], Co, Rr);       // the layer's coefficient table takes the place of (mean, invstd)
+      enc[i].mi = cbn_fwd(100 + i, pp, nm, enc[i].y, enc[i].z, Co, enc[i].R);       // the layer's coefficient table takes the place of (mean, invstd)
       if (!P->error.empty()) return P;
-    } else {
-      Op& op = b.push(F, OP_BN_FINALIZE, 100 + i);
-      op.bnf.part = part; op.bnf.mean_invstd = enc_mi[i];
-      op.bnf.running_mean = b.sptr(pp + ".1.running_mean"); op.bnf.running_var = b.sptr(pp + ".1.running_var");
-      op.bnf.nblk = cfg.training ? nblk : -1; op.bnf.C = Co; op.bnf.Cpad = g.Npad; op.bnf.count = (double)Rr;
-      op.bnf.eps = 1e-5f; op.bnf.momentum = 0.1f;
     }
-    if (!cbn) {
-      Op& op = b.push(F, OP_BN_APPLY, 100 + i);
-      op.bna.y = ency[i]; op.bna.z = encz[i]; op.bna.mean_invstd = enc_mi[i];
-      op.bna.gamma = b.pptr(pp + ".1.weight"); op.bna.beta = b.pptr(pp + ".1.bias"); op.bna.slope = b.pptr(pp + ".2.weight");
-      op.bna.R = Rr; op.bna.C = Co; op.bna.dt = adt;
-    }
-    enc[i].f[0] = g; enc[i].coef[0] = coef; enc[i].bias = bias; enc[i].C = Co; enc[i].Fq = Fo; enc[i].R = Rr;
-    prev = encz[i];
+    x = Builder::ActSrc{enc[i].z, (int64_t)T * Fo * Co, Fo * Co, 0, Co};
   }
 
   // ------------------------------------------------------------------ complex LSTM stack (tools_for_model.py:141-181)
   const int64_t BT = (int64_t)B * T;
   struct Lstm { RunGemm gx[2]; Builder::Coef cgx[2]; std::function<void(int, int32_t*)> bgx; Ptr gxb, h, gates, cst, hc; RunGemm hh[4]; Builder::Coef chh[4]; };
   std::vector<Lstm> ls(NL);
-  Ptr lin = encz[n - 1];
+  Ptr lin = enc[n - 1].z;
   // ---- cfg.lstm == 'real': two stacked real LSTM layers over all D*Cl features (feature order c*D + d, models.py:214-218)
   struct RealL { RunGemm gx, hh; Builder::Coef cgx; std::function<void(int, int32_t*)> bgx; Ptr gxb, h, gates, cst; const ParamInfo* Whh; };
   RealL rl[2];
@@ -1138,10 +1384,8 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
   }
 
   // ------------------------------------------------------------------ decoder (models.py:222-226; sub-pixel phases)
-  std::vector<Ptr> decy(n), decz(n), dec_mi(n);
-  struct DecSrc { Ptr p; int64_t bstride; int tstride, base, C; };
-  DecSrc dprev{decin, (int64_t)T * D * Cl, D * Cl, 0, Cl};
-  std::vector<std::array<DecSrc, 2>> dec_src(n);
+  std::array<Builder::ActSrc, 2> src{Builder::ActSrc{decin, (int64_t)T * D * Cl, D * Cl, 0, Cl}, Builder::ActSrc{}};
+  std::vector<std::array<Builder::ActSrc, 2>> dec_src(n);
   for (int d = 0; d < n; ++d) {
     const int idx = n - d;
     const int C0 = ch[idx], C1 = cfg.skip ? ch[idx] : 0, Co = ch[idx - 1];
@@ -1152,10 +1396,11 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
     const std::string pp = "decoder." + std::to_string(d);
     const ParamInfo &Wr = b.par(pp + ".0.real_conv.weight"), &Wi = b.par(pp + ".0.imag_conv.weight");
     const ParamInfo &br = b.par(pp + ".0.real_conv.bias"), &bi = b.par(pp + ".0.imag_conv.bias");
-    const int Co2 = Co / 2, Cin2 = (C0 + C1) / 2;
-    const int64_t Rr = (int64_t)B * (T + 1) * Fo;
-    decy[d] = b.ws(nm + ".y", Rr * Cob, adt);
-    if (!last) { decz[d] = b.ws(nm + ".z", Rr * Co, adt); dec_mi[d] = b.ws(nm + ".mi", 2 * Co, DT_F32); }
+    const int Co2 = Co / 2;
+    Builder::ConvLayer& Ly = dec[d];
+    Ly.C = Co; Ly.Fq = Fo; Ly.R = (int64_t)B * (T + 1) * Fo;
+    Ly.y = b.ws(nm + ".y", Ly.R * Cob, adt);
+    if (!last) { Ly.z = b.ws(nm + ".z", Ly.R * Co, adt); Ly.mi = b.ws(nm + ".mi", 2 * Co, DT_F32); }
     // reference input-channel index (within the real or imag half) of channel c of source s (complex_cat order)
     auto refc = [=](int s, int cc, bool& imag) {
       const int Cs = s == 0 ? C0 : C1;
@@ -1163,7 +1408,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       const int q = imag ? cc - Cs / 2 : cc;
       return s == 0 ? q : C0 / 2 + q;
     };
-    std::function<int32_t(int, int, int, int, int)> wcoef = [=](int nn, int s, int cc, int kh, int kw) -> int32_t {
+    Builder::WCoef wcoef = [=](int nn, int s, int cc, int kh, int kw) -> int32_t {
       if (nn >= Co) return 0;                        // pad output channel
       bool ii;
       const int rc = refc(s, cc, ii);
@@ -1173,16 +1418,15 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       if (!oi) return ii ? pe(Wi, ix, -1) : pe(Wr, ix, 1);
       return ii ? pe(Wr, ix, 1) : pe(Wi, ix, 1);
     };
-    std::function<void(int, int32_t*)> bias = [=](int nn, int32_t* o) {
+    Ly.bias = [=](int nn, int32_t* o) {
       if (nn >= Co) { o[0] = o[1] = 0; }
       else if (nn < Co2) { o[0] = pe(br, nn, 1); o[1] = pe(bi, nn, -1); }
       else { o[0] = pe(br, nn - Co2, 1); o[1] = pe(bi, nn - Co2, 1); }
     };
-    (void)Cin2;
     const int nblk1 = (int)(((int64_t)B * (T + 1) * Fi + kBM - 1) / kBM);
-    Ptr part = b.none();
-    int npad_stat = (int)rup(Co, bn_of(Co));
-    if (!last) part = b.ws(nm + ".stat", (int64_t)2 * nblk1 * 2 * npad_stat, DT_F32);
+    const int npad_stat = (int)rup(Co, bn_of(Co));
+    Ptr part = last ? b.none() : b.ws(nm + ".stat", (int64_t)2 * nblk1 * 2 * npad_stat, DT_F32);
+    const bool stats = !last && cfg.training && !cbn;
     // Thin layers (Cob <= SEFD_PHASE_MERGE_MAXN, default 32: dec4 and the mask layer): ONE GEMM for both sub-pixel phases - the even
     // phase's runs (input bins f-1, f, f+1, two frames), 2 * Cob output columns [phase][channel] (= bins 2f and 2f+1 of the output row:
     // contiguous in the channels-last buffer), zero weights where the odd phase has no tap.  These layers are bound by streaming the
@@ -1190,44 +1434,16 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
     // The backward reads only the per-phase coefficient functions.
     const int merge_maxn = tune_str("PHASE_MERGE_MAXN") ? atoi(tune_str("PHASE_MERGE_MAXN")) : 64;
     const bool merge = Cob <= merge_maxn && !(tune_str("WG_SWAP") && atoi(tune_str("WG_SWAP")) == 0);
-    for (int par = 0; par < 2; ++par) {
-      RunGemm g = Builder::gemm0();
-      g.xdt = adt; g.ydt = adt;
-      const int nsrc = cfg.skip ? 2 : 1;
-      DecSrc src[2] = {dprev, DecSrc{encz[idx - 1], (int64_t)T * Fi * C1, Fi * C1, 0, C1}};
-      dec_src[d] = {src[0], src[1]};
-      g.nseg = 0;
-      const int ntap = par == 0 ? 3 : 2;
-      for (int s = 0; s < nsrc; ++s) {
-        g.x[s] = src[s].p; g.bstride[s] = src[s].bstride; g.tstride[s] = src[s].tstride; g.base[s] = src[s].base;
-        g.rowlen[s] = Fi * src[s].C; g.fstride[s] = src[s].C; g.Tin[s] = T;
-        for (int kw = 0; kw < 2; ++kw) g.seg[g.nseg++] = Seg{s, -kw, par == 0 ? -src[s].C : 0, ntap * src[s].C, 0};
-      }
-      g.M = B * (T + 1) * Fi; g.Tout = T + 1; g.Fo = Fi;
-      g.N = Cob;
-      Builder::layout_segs(g);
-      const int c0 = C0, c1 = C1;
-      Builder::Coef coef = [=](int nn, int sg, int j) -> int32_t {
-        const int s = sg / 2, kw = sg % 2;
-        const int Cs = s == 0 ? c0 : c1;
-        const int jj = j / Cs, cc = j % Cs;
-        const int kh = par == 0 ? 4 - 2 * jj : 3 - 2 * jj;
-        return wcoef(nn, s, cc, kh, kw);
-      };
-      if (merge) { dec[d].f[par] = g; dec[d].coef[par] = coef; continue; }     // descriptor only (no packed weights): see below
-      b.pack_weights(F, g, coef, nm + ".p" + std::to_string(par), 400 + d, par == 0 ? &bias : nullptr);
-      if (par == 1) g.bias = dec[d].f[0].bias;
-      g.y = decy[d]; g.y_bstride = (int64_t)(T + 1) * Fo * Cob; g.y_tstride = Fo * Cob; g.y_fstride = 2 * Cob; g.y_off = par * Cob;
-      if (!last && cfg.training && !cbn) g.stats = b.mk(A_WS, part.off + (int64_t)par * nblk1 * 2 * g.Npad * 4);
-      b.push(F, OP_RUNGEMM, 400 + d).g = g;
-      dec[d].f[par] = g; dec[d].coef[par] = coef;
-    }
+    src[1] = Builder::ActSrc{enc[idx - 1].z, (int64_t)T * Fi * C1, Fi * C1, 0, C1};
+    dec_src[d] = src;
+    b.dec_phases(F, 400 + d, nm, Ly, src, Fi, Cob, wcoef, stats ? part : b.none(), nblk1, !merge);
     int fin_nblk = 2 * nblk1, fin_cpad = npad_stat, fin_nsub = 0;
     if (merge) {
-      RunGemm g = dec[d].f[0];                  // the even phase's runs
+      RunGemm g = Ly.f[0];                      // the even phase's runs
       g.N = 2 * Cob;
       Builder::layout_segs(g);
-      const Builder::Coef f0 = dec[d].coef[0], f1 = dec[d].coef[1];
+      const Builder::Coef f0 = Ly.coef[0], f1 = Ly.coef[1];
+      const Builder::Bias bias = Ly.bias;
       const int c0 = C0, c1 = C1, cob = Cob;
       Builder::Coef coef = [=](int nn, int sg, int j) -> int32_t {
         if (nn >= 2 * cob) return 0;
@@ -1235,34 +1451,24 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
         const int Cs = sg / 2 == 0 ? c0 : c1;
         return j < Cs ? 0 : f1(nn - cob, sg, j - Cs);          // the odd phase's taps are bins f, f+1: one bin into the even phase's run
       };
-      std::function<void(int, int32_t*)> bias2 = [=](int nn, int32_t* o) { if (nn >= 2 * cob) { o[0] = o[1] = 0; } else bias(nn % cob, o); };
+      Builder::Bias bias2 = [=](int nn, int32_t* o) { if (nn >= 2 * cob) { o[0] = o[1] = 0; } else bias(nn % cob, o); };
       b.pack_weights(F, g, coef, nm + ".pm", 400 + d, &bias2);
-      g.y = decy[d]; g.y_bstride = (int64_t)(T + 1) * Fo * Cob; g.y_tstride = Fo * Cob; g.y_fstride = 2 * Cob; g.y_off = 0;
-      if (!last && cfg.training && !cbn) {
+      g.y = Ly.y; g.y_bstride = (int64_t)(T + 1) * Fo * Cob; g.y_tstride = Fo * Cob; g.y_fstride = 2 * Cob; g.y_off = 0;
+      if (stats) {
         if ((int64_t)nblk1 * 2 * g.Npad > (int64_t)2 * nblk1 * 2 * npad_stat) { P->error = "merged sub-pixel GEMM: statistics pitch"; return P; }
         g.stats = part;
         fin_nblk = nblk1; fin_cpad = g.Npad; fin_nsub = 2;
       }
       b.push(F, OP_RUNGEMM, 400 + d).g = g;
     }
-    dec[d].bias = bias; dec[d].C = Co; dec[d].Fq = Fo; dec[d].R = Rr;
-    if (!last && cbn) {
-      dec_mi[d] = cbn_fwd(400 + d, pp, nm, decy[d], decz[d], Co, Rr);
+    if (last) continue;
+    if (cbn) {
+      Ly.mi = cbn_fwd(400 + d, pp, nm, Ly.y, Ly.z, Co, Ly.R);
       if (!P->error.empty()) return P;
-      dprev = DecSrc{decz[d], (int64_t)(T + 1) * Fo * Co, Fo * Co, Fo * Co, Co};
-    } else if (!last) {
-      Op& op = b.push(F, OP_BN_FINALIZE, 400 + d);
-      op.bnf.part = part; op.bnf.mean_invstd = dec_mi[d];
-      op.bnf.running_mean = b.sptr(pp + ".1.running_mean"); op.bnf.running_var = b.sptr(pp + ".1.running_var");
-      op.bnf.nblk = cfg.training ? fin_nblk : -1; op.bnf.C = Co; op.bnf.Cpad = fin_cpad; op.bnf.count = (double)Rr;
-      op.bnf.nsub = fin_nsub; op.bnf.substride = Cob;
-      op.bnf.eps = 1e-5f; op.bnf.momentum = 0.1f;
-      Op& oa = b.push(F, OP_BN_APPLY, 400 + d);
-      oa.bna.y = decy[d]; oa.bna.z = decz[d]; oa.bna.mean_invstd = dec_mi[d];
-      oa.bna.gamma = b.pptr(pp + ".1.weight"); oa.bna.beta = b.pptr(pp + ".1.bias"); oa.bna.slope = b.pptr(pp + ".2.weight");
-      oa.bna.R = Rr; oa.bna.C = Co; oa.bna.dt = adt;
-      dprev = DecSrc{decz[d], (int64_t)(T + 1) * Fo * Co, Fo * Co, Fo * Co, Co};   // frames 1..T of the T+1 buffer
+    } else {
+      b.bn_fwd(F, 400 + d, pp, Ly, part, fin_nblk, fin_cpad, fin_nsub, Cob);
     }
+    src[0] = Builder::ActSrc{Ly.z, (int64_t)(T + 1) * Fo * Co, Fo * Co, Fo * Co, Co};   // frames 1..T of the T+1 buffer
   }
 
   // ------------------------------------------------------------------ mask, iSTFT, outputs (models.py:253-282)
@@ -1272,29 +1478,12 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
   std::memset(&mk, 0, sizeof(mk));
   {
     const int Fo = Fe[0], Co = std::max(2, CP);
-    mk.spec = spec; mk.mask = decy[n - 1]; mk.est = est; mk.dest = mk.dmask = b.none();
+    mk.spec = spec; mk.mask = dec[n - 1].y; mk.est = est; mk.dest = mk.dmask = b.none();
     mk.frames = BT; mk.NF = NF; mk.mode = cfg.mask_mode; mk.mdt = adt; mk.mch = Co; mk.estm = mk.destm = b.none();
     mk.mask_fstride = (int64_t)Fo * Co; mk.mask_bstride = (int64_t)(T + 1) * Fo * Co; mk.mask_base = (int64_t)Fo * Co; mk.T = T;
     b.push(F, OP_MASK_FWD, 500).mask = mk;
   }
-  RunGemm gi = Builder::gemm0();
-  if (!b.istft_fft(F, 501, est, frames, BT, NFFT, win)) {
-    RunGemm& g = gi;
-    g.x[0] = est; g.xdt = DT_F32; g.ydt = DT_F32;
-    g.bstride[0] = (int64_t)T * SW; g.tstride[0] = SW; g.rowlen[0] = SW; g.Tin[0] = T;
-    g.M = (int)BT; g.Tout = T; g.Fo = 1;
-    g.nseg = 1; g.seg[0] = Seg{0, 0, 0, SW, 0};
-    g.N = W;
-    Builder::layout_segs(g);
-    const_weights(g, [&](int nn, int j) { return j < 2 ? 0.0 : Kinv[((size_t)(j & 1) * NF + (j / 2 - 1)) * W + nn]; });
-    g.y = frames; g.y_bstride = (int64_t)T * W; g.y_tstride = W;
-    b.push(F, OP_RUNGEMM, 501).g = g;
-  }
-  Ola ola;
-  std::memset(&ola, 0, sizeof(ola));
-  ola.frames = frames; ola.wav = io_out; ola.coff = c_coff; ola.dwav = ola.dpad = b.none();
-  ola.B = B; ola.T = T; ola.L = L; ola.win = W; ola.hop = hop; ola.trim = trim;
-  b.push(F, OP_OLA_FWD, 502).ola = ola;
+  const Ola ola = b.istft_ola(F, est, frames, io_out);
   SpecOut so;
   std::memset(&so, 0, sizeof(so));
   so.est = est; so.out_real = io_or; so.out_imag = io_oi; so.B = B; so.T = T; so.NF = NF; so.accumulate = 0;
@@ -1302,42 +1491,13 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
 
   // =================================================================================================== backward
   if (cfg.training) {
-    Ptr dpad = b.ws("dpad", (int64_t)B * Lp, DT_F32);
-    Ptr dest = b.ws("dest", BT * SW, DT_F32);
+    Ptr dest = b.istft_ola_bwd(R, ola, io_gw);
     {
-      Ola o = ola;
-      o.dwav = io_gw; o.dpad = dpad;
-      b.push(R, OP_OLA_BWD, 502).ola = o;
-      if (!b.istft_bwd_fft(R, 501, dpad, dest, B, Lp, T, hop, NFFT, win)) {
-        RunGemm g = Builder::gemm0();
-        g.x[0] = dpad; g.xdt = DT_F32; g.ydt = DT_F32;
-        g.bstride[0] = Lp; g.tstride[0] = 0; g.rowlen[0] = Lp; g.fstride[0] = hop; g.Tin[0] = 1;
-        g.M = (int)BT; g.Tout = 1; g.Fo = T;
-        g.nseg = 1; g.seg[0] = Seg{0, 0, 0, W, 0};
-        g.N = SW;
-        Builder::layout_segs(g);
-        const_weights(g, [&](int nn, int j) { return nn < 2 ? 0.0 : Kinv[((size_t)(nn & 1) * NF + (nn / 2 - 1)) * W + j]; });
-        g.y = dest; g.y_bstride = (int64_t)T * SW; g.y_fstride = SW;
-        b.push(R, OP_RUNGEMM, 501).g = g;
-      }
       SpecOut s2 = so;
       s2.est = dest; s2.out_real = io_gr; s2.out_imag = io_gi; s2.accumulate = 1;
       b.push(R, OP_SPECOUT_BWD, 503).so = s2;
     }
-    // gradient buffers
-    std::vector<Ptr> d_decy(n), d_decz(n), d_skip(n), d_encz(n), d_ency(n);
-    for (int d = 0; d < n; ++d) {
-      const int idx = n - d;
-      const int Co = idx == 1 ? std::max(ch[idx - 1], CP) : ch[idx - 1], Fo = 2 * Fe[idx];
-      d_decy[d] = b.ws("dec" + std::to_string(d) + ".dy", (int64_t)B * (T + 1) * Fo * Co, adt);
-      if (idx != 1) d_decz[d] = b.ws("dec" + std::to_string(d) + ".dz", (int64_t)B * T * Fo * Co, adt);
-    }
-    for (int i = 0; i < n; ++i) {
-      const int64_t e = (int64_t)B * T * Fe[i + 1] * ch[i + 1];
-      d_ency[i] = b.ws("enc" + std::to_string(i) + ".dy", e, adt);
-      d_encz[i] = b.ws("enc" + std::to_string(i) + ".dz", e, adt);
-      if (cfg.skip) d_skip[i] = b.ws("enc" + std::to_string(i) + ".dskip", e, adt);
-    }
+    b.conv_grads(enc, dec, std::max(ch[0], CP));
     constexpr int kCsRows = 2048;                // workgroups of MASK_BWD when it also leaves the mask layer's bias-gradient shares
     const bool mask_colsum = !(tune_str("MASK_COLSUM") && atoi(tune_str("MASK_COLSUM")) == 0) && CP >= 2 && CP <= 8 &&
                              !(tune_str("WG_SWAP") && atoi(tune_str("WG_SWAP")) == 0);
@@ -1345,7 +1505,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
     Ptr d_decin = b.ws("decin.d", BT * D * Cl, adt);
     {
       Mask m2 = mk;
-      m2.dest = dest; m2.dmask = d_decy[n - 1];
+      m2.dest = dest; m2.dmask = dec[n - 1].dy;
       if (mask_colsum) { m2.colsum_rows = kCsRows; mask_colsum_op = (int)R.size(); }
       b.push(R, OP_MASK_BWD, 500).mask = m2;
     }
@@ -1361,7 +1521,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
     const int bn_fuse_mode = tune_str("BN_FUSE") ? atoi(tune_str("BN_FUSE")) : 1;
     const bool bn_fuse = bn_fuse_mode != 0 && !cbn;
     auto bn_fuse_layer = [&](int C, int64_t Rr) { return bn_fuse_mode == 2 || (adt == DT_BF16 && C % 256 == 0 && Rr >= 8192); };
-    struct BnbAcc { Ptr part; int rows = 0, cap = 0, ldp = 0; bool on = false; Ptr y, mi; std::string pp; };
+    using BnbAcc = Builder::BnbAcc;
     std::vector<BnbAcc> bnb_dec(n), bnb_enc(n);
     auto bnb_init = [&](BnbAcc& a, const std::string& nm, Ptr y, Ptr mi, const std::string& pp, int C, int64_t Rr) {
       a.on = true; a.y = y; a.mi = mi; a.pp = pp;
@@ -1370,8 +1530,8 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       a.part = b.ws(nm + ".bnpart", (int64_t)a.cap * 3 * a.ldp, DT_F32);
     };
     if (bn_fuse) {
-      for (int d = 0; d + 1 < n; ++d) if (bn_fuse_layer(dec[d].C, dec[d].R)) bnb_init(bnb_dec[d], "dec" + std::to_string(d), decy[d], dec_mi[d], "decoder." + std::to_string(d), dec[d].C, dec[d].R);
-      for (int i = 0; i + 1 < n; ++i) if (bn_fuse_layer(enc[i].C, enc[i].R)) bnb_init(bnb_enc[i], "enc" + std::to_string(i), ency[i], enc_mi[i], "encoder." + std::to_string(i), enc[i].C, enc[i].R);
+      for (int d = 0; d + 1 < n; ++d) if (bn_fuse_layer(dec[d].C, dec[d].R)) bnb_init(bnb_dec[d], "dec" + std::to_string(d), dec[d].y, dec[d].mi, "decoder." + std::to_string(d), dec[d].C, dec[d].R);
+      for (int i = 0; i + 1 < n; ++i) if (bn_fuse_layer(enc[i].C, enc[i].R)) bnb_init(bnb_enc[i], "enc" + std::to_string(i), enc[i].y, enc[i].mi, "encoder." + std::to_string(i), enc[i].C, enc[i].R);
     }
     // the GEMM `g` writes dz rows (b, u, fo) of that layer; (bs, ts, fs, off) address the same rows of the layer's forward output y
     auto bnb_attach = [&](RunGemm& g, BnbAcc& a, int64_t bs, int ts, int fs, int off) {
@@ -1385,49 +1545,6 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       g.stats = b.mk(A_WS, a.part.off + (int64_t)a.rows * 3 * a.ldp * 4);
       a.rows += rows;
     };
-    BnBwdApply last_bnb;                         // the BnBwdApply of the most recent bn_bwd (the fused first-layer weight gradient reads its totals)
-    std::memset(&last_bnb, 0, sizeof(last_bnb));
-    auto bn_bwd = [&](int tag, Ptr y, Ptr dz0, Ptr dz1, Ptr mi, const std::string& pp, int C, int64_t Rr, int64_t rpb, int skip, Ptr dy,
-                      const std::string& nm, const BnbAcc* fused, bool no_apply = false) {
-      int64_t rpbk = std::max<int64_t>(64, (Rr + 2047) / 2048);
-      const int nblk = (int)((Rr + rpbk - 1) / rpbk);
-      if (cbn) {                                  // `mi` is the layer's coefficient table (cbn_fwd)
-        const int h = C / 2;
-        CbnBwd c;
-        std::memset(&c, 0, sizeof(c));
-        c.y = y; c.dz0 = dz0; c.dz1 = dz1; c.dy = dy; c.coef = mi;
-        c.coefb = b.ws(nm + ".ccoefb", 9 * h, DT_F32);
-        c.part = b.ws(nm + ".cbnpart", (int64_t)nblk * 7 * h, DT_F32);
-        const char* wn[3] = {"Wrr", "Wri", "Wii"};
-        for (int q = 0; q < 3; ++q) { c.W[q] = b.pptr(pp + ".1." + wn[q]); c.dW[q] = b.pptr(pp + ".1." + wn[q], A_GRAD); }
-        c.dB[0] = b.pptr(pp + ".1.Br", A_GRAD); c.dB[1] = b.pptr(pp + ".1.Bi", A_GRAD);
-        c.slope = b.pptr(pp + ".2.weight"); c.dslope = b.pptr(pp + ".2.weight", A_GRAD);
-        c.R = Rr; c.rpb = rpb; c.C = C; c.dt = adt; c.nblk = nblk; c.rows_per_blk = (int)rpbk; c.skip = skip; c.count = (double)Rr;
-        b.push(R, OP_CBN_BWD_REDUCE, tag).cbb = c;
-        b.push(R, OP_CBN_BWD_FINALIZE, tag).cbb = c;
-        b.push(R, OP_CBN_BWD_APPLY, tag).cbb = c;
-        return;
-      }
-      BnBwdReduce r;
-      std::memset(&r, 0, sizeof(r));
-      r.y = y; r.dz0 = dz0; r.dz1 = dz1; r.mean_invstd = mi;
-      r.gamma = b.pptr(pp + ".1.weight"); r.beta = b.pptr(pp + ".1.bias"); r.slope = b.pptr(pp + ".2.weight");
-      r.R = Rr; r.C = C; r.dt = adt; r.nblk = nblk; r.rows_per_blk = (int)rpbk; r.rpb = rpb; r.skip = skip;
-      if (fused && fused->on) {                   // the producers' epilogues wrote the partial rows
-        r.part = fused->part; r.nblk = fused->rows; r.ldp = fused->ldp;
-      } else {
-        r.part = b.ws(nm + ".bnpart", (int64_t)nblk * 3 * C, DT_F32);
-        b.push(R, OP_BN_BWD_REDUCE, tag).bnr = r;
-      }
-      BnBwdApply a;
-      std::memset(&a, 0, sizeof(a));
-      a.r = r; a.totals = b.ws(nm + ".bntot", 3 * C, DT_F32); a.dy = dy;
-      a.dgamma = b.pptr(pp + ".1.weight", A_GRAD); a.dbeta = b.pptr(pp + ".1.bias", A_GRAD); a.dslope = b.pptr(pp + ".2.weight", A_GRAD);
-      a.count = (double)Rr;
-      b.push(R, OP_BN_BWD_FINALIZE, tag).bnb = a;
-      if (!no_apply) b.push(R, OP_BN_BWD_APPLY, tag).bnb = a;
-      last_bnb = a;
-    };
 
     // ---- decoder backward
     for (int d = n - 1; d >= 0; --d) {
@@ -1439,7 +1556,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       const std::string nm = "dec" + std::to_string(d);
       const std::string pp = "decoder." + std::to_string(d);
       if (!last)
-        bn_bwd(400 + d, decy[d], d_decz[d], b.none(), dec_mi[d], pp, Co, dec[d].R, (int64_t)(T + 1) * Fo, Fo, d_decy[d], nm, &bnb_dec[d]);
+        b.bn_bwd(R, 400 + d, dec[d].y, dec[d].dz, b.none(), dec[d].mi, pp, Co, dec[d].R, (int64_t)(T + 1) * Fo, Fo, dec[d].dy, nm, cbn, &bnb_dec[d], false);
       // Weight gradients.  Forward form (SEFD_WG_SWAP=0): one WGRAD per sub-pixel phase, A = the forward runs (3 or 2 taps x C channels of
       // both sources, two frames: every input element is streamed through LDS ~5 times per phase pair), dense operand = dy.
       // Swapped form (default): the SAME tensor, contracted over INPUT pixels - dense operand = the source activation x_s (each element
@@ -1450,7 +1567,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       // computes as rounding noise and this plan leaves at exactly 0.
       const bool wg_swap = !(tune_str("WG_SWAP") && atoi(tune_str("WG_SWAP")) == 0);
       b.cur_lane = 1;                           // weight gradients of the decoder: nothing downstream needs them before UNPACK
-      if (!wg_swap) for (int par = 0; par < 2; ++par) b.wgrad(R, dec[d].f[par], d_decy[d], dec[d].coef[par], 400 + d, &dec[d].bias);
+      if (!wg_swap) for (int par = 0; par < 2; ++par) b.wgrad(R, dec[d].f[par], dec[d].dy, dec[d].coef[par], 400 + d, &dec[d].bias);
       else if (!last) {                          // conv biases in front of BatchNorm: UNPACK writes their exact zero
         b.zero_grad.resize(nparam, 0);
         for (const char* part : {".0.real_conv.bias", ".0.imag_conv.bias"}) {
@@ -1480,7 +1597,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
         fb.nseg = 0; fb.N = Co;
         fb.y_bstride = (int64_t)(T + 1) * Fo * Co; fb.y_tstride = Fo * Co; fb.y_fstride = Co; fb.y_off = 0;
         Builder::Coef none_coef = [](int, int, int) -> int32_t { return 0; };
-        b.wgrad(R, fb, d_decy[d], none_coef, 400 + d, &dec[d].bias);
+        b.wgrad(R, fb, dec[d].dy, none_coef, 400 + d, &dec[d].bias);
       }
       b.cur_lane = 0;
       // input gradients: conv-form over dy [B][T+1][Fo][Co]; dx[ci,f,t] = sum W[ci,co,kh,kw] dy[co, 2f+kh-2, t+kw]
@@ -1494,32 +1611,8 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       Builder::Coef dg_coef[2];
       for (int s = 0; s < nsrc; ++s) {
         const int Cs = s == 0 ? C0 : C1;
-        RunGemm g = Builder::gemm0();
-        g.x[0] = d_decy[d]; g.xdt = adt; g.ydt = adt;
-        g.bstride[0] = (int64_t)(T + 1) * Fo * Co; g.tstride[0] = Fo * Co; g.base[0] = 0; g.rowlen[0] = Fo * Co; g.fstride[0] = 2 * Co; g.Tin[0] = T + 1;
-        g.M = B * T * Fi; g.Tout = T; g.Fo = Fi;
-        g.nseg = 2;
-        g.seg[0] = Seg{0, 0, -2 * Co, KS * Co, 0};    // kw = 0 : buffer frame u = t
-        g.seg[1] = Seg{0, 1, -2 * Co, KS * Co, 0};    // kw = 1 : buffer frame u = t + 1
-        g.N = Cs;
-        Builder::layout_segs(g);
-        // d y[co] / d x[(s,cc)] is the forward coefficient of phase (kh odd) at tap jj: look it up in the forward tables
-        const Builder::Coef f0 = dec[d].coef[0], f1 = dec[d].coef[1];
-        const int Csx = Cs;
-        Builder::Coef coef = [=](int nn, int sg, int j) -> int32_t {
-          const int kw = sg, kh = j / Co, co = j % Co;
-          const int par = kh & 1;
-          const int jj = par == 0 ? (4 - kh) / 2 : (3 - kh) / 2;
-          return (par == 0 ? f0 : f1)(co, s * 2 + kw, jj * Csx + nn);
-        };
-        if (!dg_merge) b.pack_weights(R, g, coef, nm + ".dg" + std::to_string(s), 400 + d);
-        if (s == 0) {
-          if (d > 0) { g.y = d_decz[d - 1]; }
-          else g.y = d_decin;
-        } else {
-          g.y = d_skip[idx - 1];
-        }
-        g.y_bstride = (int64_t)T * Fi * Cs; g.y_tstride = Fi * Cs; g.y_fstride = Cs; g.y_off = 0;
+        Builder::Coef coef;
+        RunGemm g = b.dec_dgrad(R, 400 + d, nm, dec[d], Co, Fi, s, Cs, s == 0 ? (d > 0 ? dec[d - 1].dz : d_decin) : enc[idx - 1].dskip, coef, !dg_merge);
         // dz of the previous decoder layer (its y keeps the frame that `[..., 1:]` drops: rows start one frame in) / of encoder layer idx-1
         if (s == 0 && d > 0) bnb_attach(g, bnb_dec[d - 1], (int64_t)(T + 1) * Fi * Cs, Fi * Cs, Cs, Fi * Cs);
         else if (s == 1) bnb_attach(g, bnb_enc[idx - 1], (int64_t)T * Fi * Cs, Fi * Cs, Cs, 0);
@@ -1528,7 +1621,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
         if (wg_swap) {                           // weight gradient, swapped form: the runs of this GEMM against the source activation
           RunGemm fw = g;
           fw.flags = 0; fw.stats = b.none(); fw.bias = b.none(); fw.ydt = adt;
-          const DecSrc& xs = dec_src[d][s];
+          const Builder::ActSrc& xs = dec_src[d][s];
           fw.y_bstride = xs.bstride; fw.y_tstride = xs.tstride; fw.y_fstride = xs.C; fw.y_off = xs.base;
           b.cur_lane = 1;
           b.wgrad(R, fw, xs.p, coef, 400 + d, nullptr);
@@ -1626,7 +1719,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
           const Builder::Coef cf = Lr.cgx;
           Builder::Coef coef = [=](int nn, int sg, int j) -> int32_t { return l == 0 ? cf(j, q, nn) : cf(j, 0, nn); };
           b.pack_weights(R, g, coef, nm + ".dx" + std::to_string(q), 200 + l);
-          if (l == 0) { g.ydt = adt; g.y = d_encz[n - 1]; g.y_bstride = (int64_t)T * D * Cl; g.y_tstride = D * Cl; g.y_off = q * Cl; }
+          if (l == 0) { g.ydt = adt; g.y = enc[n - 1].dz; g.y_bstride = (int64_t)T * D * Cl; g.y_tstride = D * Cl; g.y_off = q * Cl; }
           else { g.ydt = DT_F32; g.y = dh[0]; g.y_bstride = (int64_t)T * H; g.y_tstride = H; }
           b.push(R, OP_RUNGEMM, 200 + l).g = g;
         }
@@ -1765,7 +1858,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
           return (p == 0 ? cf0 : cf1)(j, q, c);
         };
         b.pack_weights(R, g, coef, nm + ".dxm", 200 + l);
-        g.y = d_encz[n - 1]; g.y_bstride = (int64_t)T * D * Cl; g.y_tstride = D * Cl; g.y_off = 0;
+        g.y = enc[n - 1].dz; g.y_bstride = (int64_t)T * D * Cl; g.y_tstride = D * Cl; g.y_off = 0;
         b.push(R, OP_RUNGEMM, 200 + l).g = g;
       }
       for (int p = 0; p < (dx_merge ? 0 : 2); ++p) {
@@ -1782,7 +1875,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
           Builder::Coef coef = [=](int nn, int sg, int j) -> int32_t { return l == 0 ? cf(j, q, nn) : cf(j, 0, nn); };
           b.pack_weights(R, g, coef, nm + ".dx" + std::to_string(p) + "_" + std::to_string(q), 200 + l);
           if (l == 0) {
-            g.ydt = adt; g.y = d_encz[n - 1];
+            g.ydt = adt; g.y = enc[n - 1].dz;
             g.y_bstride = (int64_t)T * D * Cl; g.y_tstride = D * Cl; g.y_off = q * Cl + p * (Cl / 2);
           } else {
             g.ydt = DT_F32; g.y = dx_full;
@@ -1821,7 +1914,8 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       // the MAIN stream right behind BN_BWD_FINALIZE: apply (117 us) -> fold -> weight gradient (52 us) was the serial tail of the step.  ENC0_BNFUSE=0: off
       const bool dy_fused = i == 0 && (enc[0].f[0].flags & kRunEnc0) && enc0_accepts(enc[0].f[0], true) && !cbn &&    // (its weight gradient's form: sefd_desc.h)
                             !(tune_str("ENC0_BNFUSE") && atoi(tune_str("ENC0_BNFUSE")) == 0);
-      bn_bwd(100 + i, ency[i], d_encz[i], cfg.skip ? d_skip[i] : b.none(), enc_mi[i], pp, Co, enc[i].R, (int64_t)T * Fo, 0, d_ency[i], nm, &bnb_enc[i], dy_fused);
+      const BnBwdApply bnb = b.bn_bwd(R, 100 + i, enc[i].y, enc[i].dz, cfg.skip ? enc[i].dskip : b.none(), enc[i].mi, pp, Co, enc[i].R, (int64_t)T * Fo, 0,
+                                      enc[i].dy, nm, cbn, &bnb_enc[i], dy_fused);
       // the folds of enc5 .. enc1 go in front of the LAST weight gradient on its lane (its input is the last thing the dgrad chain produces,
       // the lane usually waits for it): the fold in front of the final UNPACK then covers one thin layer
       if (i == 0 && lane_all && n > 1 && !(tune_str("SPLITSUM_MID") && atoi(tune_str("SPLITSUM_MID")) == 0)) b.flush_sums(R, 996, true);
@@ -1837,18 +1931,18 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
           for (int64_t e = 0; e < pb.numel; ++e) b.zero_grad[pb.off + e] = 1;
         }
       }
-      b.wgrad(R, enc[i].f[0], dy_fused ? d_encz[i] : d_ency[i], enc[i].coef[0], 100 + i, enc_bias_zero ? nullptr : &enc[i].bias);
+      b.wgrad(R, enc[i].f[0], dy_fused ? enc[i].dz : enc[i].dy, enc[i].coef[0], 100 + i, enc_bias_zero ? nullptr : &enc[i].bias);
       if (dy_fused) {
         for (size_t q = R.size(); q-- > 0;)
           if (R[q].kind == OP_WGRAD && R[q].tag == 100 + i) {
             RunGemm& g = R[q].g;
             g.flags |= kRunDyFromBn;
-            g.bnb_dz1 = cfg.skip ? d_skip[i] : b.none();
-            g.bnb_y = ency[i]; g.bnb_mi = enc_mi[i];
+            g.bnb_dz1 = cfg.skip ? enc[i].dskip : b.none();
+            g.bnb_y = enc[i].y; g.bnb_mi = enc[i].mi;
             g.bnb_gamma = b.pptr(pp + ".1.weight"); g.bnb_beta = b.pptr(pp + ".1.bias"); g.bnb_slope = b.pptr(pp + ".2.weight");
             g.bnb_bstride = g.y_bstride; g.bnb_tstride = g.y_tstride; g.bnb_fstride = g.y_fstride; g.bnb_off = g.y_off;
             // per-rank count: like every descriptor that carries a BatchNorm count, this one must be scaled by the SyncBN post-pass (finalize_rungemms)
-            g.bnb_totals = last_bnb.totals; g.bnb_inv_count = (float)(1.0 / last_bnb.count);
+            g.bnb_totals = bnb.totals; g.bnb_inv_count = (float)(1.0 / bnb.count);
             break;
           }
       }
@@ -1860,7 +1954,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       const int merge_maxn = tune_str("PHASE_MERGE_MAXN") ? atoi(tune_str("PHASE_MERGE_MAXN")) : 64;
       if (Ci <= merge_maxn && !bnb_enc[i - 1].on) {
         RunGemm g = Builder::gemm0();
-        g.x[0] = d_ency[i]; g.xdt = adt; g.ydt = adt;
+        g.x[0] = enc[i].dy; g.xdt = adt; g.ydt = adt;
         g.bstride[0] = (int64_t)T * Fo * Co; g.tstride[0] = Fo * Co; g.rowlen[0] = Fo * Co; g.fstride[0] = Co; g.Tin[0] = T;
         g.M = B * T * Fo; g.Tout = T; g.Fo = Fo;
         g.nseg = 2;
@@ -1876,29 +1970,12 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
           return cf(co, kw, kh * Ci + nn % Ci);
         };
         b.pack_weights(R, g, coef, nm + ".dgm", 100 + i);
-        g.y = d_encz[i - 1]; g.y_bstride = (int64_t)T * Fi * Ci; g.y_tstride = Fi * Ci; g.y_fstride = 2 * Ci; g.y_off = 0;
+        g.y = enc[i - 1].dz; g.y_bstride = (int64_t)T * Fi * Ci; g.y_tstride = Fi * Ci; g.y_fstride = 2 * Ci; g.y_off = 0;
         b.push(R, OP_RUNGEMM, 100 + i).g = g;
         continue;
       }
       for (int par = 0; par < 2; ++par) {
-        RunGemm g = Builder::gemm0();
-        g.x[0] = d_ency[i]; g.xdt = adt; g.ydt = adt;
-        g.bstride[0] = (int64_t)T * Fo * Co; g.tstride[0] = Fo * Co; g.rowlen[0] = Fo * Co; g.fstride[0] = Co; g.Tin[0] = T;
-        g.M = B * T * Fo; g.Tout = T; g.Fo = Fo;           // Fi/2 == Fo output rows per phase
-        const int ntap = par == 0 ? 3 : 2;
-        g.nseg = 2;
-        g.seg[0] = Seg{0, 1, par == 0 ? -Co : 0, ntap * Co, 0};   // kw = 0 : frame t+1
-        g.seg[1] = Seg{0, 0, par == 0 ? -Co : 0, ntap * Co, 0};   // kw = 1 : frame t
-        g.N = Ci;
-        Builder::layout_segs(g);
-        const Builder::Coef cf = enc[i].coef[0];
-        Builder::Coef coef = [=](int nn, int sg, int j) -> int32_t {
-          const int kw = sg, jj = j / Co, co = j % Co;
-          const int kh = par == 0 ? 4 - 2 * jj : 3 - 2 * jj;
-          return cf(co, kw, kh * Ci + nn);
-        };
-        b.pack_weights(R, g, coef, nm + ".dg" + std::to_string(par), 100 + i);
-        g.y = d_encz[i - 1]; g.y_bstride = (int64_t)T * Fi * Ci; g.y_tstride = Fi * Ci; g.y_fstride = 2 * Ci; g.y_off = par * Ci;
+        RunGemm g = b.enc_dgrad(R, 100 + i, nm, enc[i], Ci, Fi, par, enc[i - 1].dz);
         bnb_attach(g, bnb_enc[i - 1], (int64_t)T * Fi * Ci, Fi * Ci, 2 * Ci, par * Ci);      // rows of encoder layer i-1's output, this phase's bins
         b.push(R, OP_RUNGEMM, 100 + i).g = g;
       }
@@ -1906,15 +1983,9 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
     b.finish_unpack(R);
   }
 
-  finalize_rungemms(b, P);
+  finish_plan(b, P, nparam, nstate);
   for (size_t k = 0; k < P->bwd.size(); ++k)
     if (P->bwd[k].kind == OP_UNPACK && P->bwd[k].tag == 998) P->bucket_op = (int32_t)k;
-  P->arena_bytes[A_WS] = b.ws_off;
-  P->arena_bytes[A_PARAM] = nparam * 4;
-  P->arena_bytes[A_GRAD] = nparam * 4;
-  P->arena_bytes[A_STATE] = std::max<int64_t>(nstate, 1) * 4;
-  P->arena_bytes[A_CONST] = (int64_t)P->consts.size();
-  P->arena_bytes[A_IO] = b.io_off;
   return P;
 }
 
@@ -1930,12 +2001,9 @@ Plan* build_crn_plan(const ModelConfig& cfg) {
   Builder b;
   b.P = P;
   b.c = cfg;
+  b.fe = Stft(cfg);
   const int n = cfg.n_layers;
-  const int B = cfg.B, L = cfg.L, W = cfg.win_len, hop = cfg.hop, NFFT = cfg.fft_len;
-  const int trim = W - hop;
-  const int T = (L + 2 * trim - W) / hop + 1;
-  const int NF = NFFT / 2 + 1, NS = NF + 1, SW = NS * 2;
-  const int Lp = (T - 1) * hop + W;
+  const int B = cfg.B, T = b.fe.T, NF = b.fe.NF, SW = b.fe.SW;
   const int adt = cfg.act_dtype;
   const int KS = cfg.kernel_size;
   const int MS = NF + 7, MO = 7;            // magnitude rows: bin k at element k + 7 -> bin 1 is 16-byte aligned in fp32 and bf16
@@ -1991,71 +2059,24 @@ Plan* build_crn_plan(const ModelConfig& cfg) {
   const int64_t nstate = P->state.empty() ? 0 : P->state.back().off + P->state.back().numel;
   b.inv.resize(nparam);
 
-  Ptr io_wav = b.io("wav", (int64_t)B * L);
-  Ptr io_out = b.io("out_wav", (int64_t)B * L);
+  Ptr io_wav = b.io("wav", (int64_t)B * cfg.L);
+  Ptr io_out = b.io("out_wav", (int64_t)B * cfg.L);
   Ptr io_or = b.io("out_real", (int64_t)B * NF * T);      // est_mags
   Ptr io_oi = b.io("out_imag", (int64_t)B * NF * T);      // target_mags
-  Ptr io_gw = b.io("grad_wav", (int64_t)B * L);
+  Ptr io_gw = b.io("grad_wav", (int64_t)B * cfg.L);
   Ptr io_gr = b.io("grad_real", (int64_t)B * NF * T);     // gradient w.r.t. est_mags (crn_direct_train's loss lives there)
   b.io("grad_imag", (int64_t)B * NF * T);
-  Ptr io_tgt = b.io("tgt", (int64_t)B * L);
-
-  std::vector<double> win(W);
-  for (int j = 0; j < W; ++j) win[j] = window_value(cfg, j, W);    // win_type None: np.ones (tools_for_model.py:17-18)
-  auto Kun = [&](int part, int k, int j) {
-    const double ang = 2.0 * kPi * (double)(((int64_t)k * j) % NFFT) / NFFT;
-    return part == 0 ? std::cos(ang) : -std::sin(ang);
-  };
-  std::vector<double> Kinv((size_t)2 * NF * W);
-  {
-    const double ne = (W + 1) / 2, no = W / 2;
-    for (int part = 0; part < 2; ++part)
-      for (int k = 0; k < NF; ++k) {
-        double se = 0, so = 0;
-        for (int m = 0; m < W; ++m) (m % 2 == 0 ? se : so) += Kun(part, k, m);
-        for (int j = 0; j < W; ++j) {
-          const double corr = (j % 2 == 0) ? se / (NFFT / 2.0 + ne) : so / (NFFT / 2.0 + no);
-          Kinv[((size_t)part * NF + k) * W + j] = (Kun(part, k, j) - corr) / (NFFT / 2.0) * win[j];
-        }
-      }
-  }
-  std::vector<float> coff(Lp, 0.f);
-  {
-    std::vector<float> w2(W);
-    for (int j = 0; j < W; ++j) { const float wf = (float)win[j]; w2[j] = wf * wf; }
-    for (int t = 0; t < T; ++t)
-      for (int j = 0; j < W; ++j) coff[t * hop + j] += w2[j];
-  }
-  Ptr c_coff = b.cst(coff.data(), (int64_t)coff.size() * 4);
-  auto const_weights = [&](RunGemm& g, const std::function<double(int n, int j)>& val) {
-    std::vector<float> wt((size_t)g.Npad * g.ldw, 0.f);
-    for (int nn = 0; nn < g.N; ++nn)
-      for (int j = 0; j < g.seg[0].len; ++j) wt[(size_t)nn * g.ldw + j] = (float)val(nn, j);
-    g.w = b.cst(wt.data(), (int64_t)wt.size() * 4);
-  };
+  Ptr io_tgt = b.io("tgt", (int64_t)B * cfg.L);
+  b.synthesis();
   std::vector<Op>& F = P->fwd;
   std::vector<Op>& R = P->bwd;
   const int64_t BT = (int64_t)B * T;
 
-  // ---- STFT of the noisy input and of the target (CRN.forward always does both, models.py:468, 505)
+  // ---- STFT of the noisy input and of the target (CRN.forward always does both, models.py:468, 505; both take the same form)
   Ptr spec = b.ws("spec", BT * SW, DT_F32);
   Ptr spec_t = b.ws("spec_t", BT * SW, DT_F32);
-  if (b.stft_fft(F, 1, io_wav, spec, B, L, T, hop, trim, NFFT, win)) {
-    b.stft_fft(F, 2, io_tgt, spec_t, B, L, T, hop, trim, NFFT, win);
-  } else {
-    RunGemm g = Builder::gemm0();
-    g.x[0] = io_wav; g.xdt = DT_F32; g.ydt = DT_F32;
-    g.bstride[0] = L; g.rowlen[0] = L; g.fstride[0] = hop; g.Tin[0] = 1;
-    g.M = (int)BT; g.Tout = 1; g.Fo = T;
-    g.nseg = 1; g.seg[0] = Seg{0, 0, -trim, W, 0};
-    g.N = SW;
-    Builder::layout_segs(g);
-    const_weights(g, [&](int nn, int j) { return nn < 2 ? 0.0 : Kun(nn & 1, nn / 2 - 1, j) * win[j]; });
-    g.y = spec; g.y_bstride = (int64_t)T * SW; g.y_fstride = SW;
-    b.push(F, OP_RUNGEMM, 1).g = g;
-    g.x[0] = io_tgt; g.y = spec_t;
-    b.push(F, OP_RUNGEMM, 2).g = g;
-  }
+  b.stft_fwd(F, 1, io_wav, spec);
+  b.stft_fwd(F, 2, io_tgt, spec_t);
   Ptr mags = b.ws("mags", BT * MS, adt);
   {
     Op& op = b.push(F, OP_MAGS, 3);
@@ -2063,54 +2084,19 @@ Plan* build_crn_plan(const ModelConfig& cfg) {
   }
 
   // ---- encoder (RealConv2d, tools_for_model.py:341-386)
-  struct Layer { RunGemm f[2]; Builder::Coef coef[2]; std::function<void(int, int32_t*)> bias; int C, Fq; int64_t R; };
-  std::vector<Layer> enc(n), dec(n);
-  std::vector<Ptr> encz(n), ency(n), enc_mi(n);
-  Ptr prev = mags;
+  std::vector<Builder::ConvLayer> enc(n), dec(n);
+  Builder::ActSrc x{mags, (int64_t)T * MS, MS, MO + 1, 1};
   for (int i = 0; i < n; ++i) {
-    const int Ci = ch[i], Co = ch[i + 1], Fi = Fe[i], Fo = Fe[i + 1];
-    const std::string nm = "enc" + std::to_string(i);
+    const int Ci = ch[i], Co = ch[i + 1], Fo = Fe[i + 1];
     const std::string pp = "encoder." + std::to_string(i);
     const ParamInfo &Wc = b.par(pp + ".0.conv.weight"), &bc = b.par(pp + ".0.conv.bias");
-    RunGemm g = Builder::gemm0();
-    g.x[0] = prev; g.xdt = adt; g.ydt = adt;
-    if (i == 0) { g.bstride[0] = (int64_t)T * MS; g.tstride[0] = MS; g.base[0] = MO + 1; }
-    else { g.bstride[0] = (int64_t)T * Fi * Ci; g.tstride[0] = Fi * Ci; g.base[0] = 0; }
-    g.rowlen[0] = Fi * Ci; g.fstride[0] = 2 * Ci; g.Tin[0] = T;
-    g.M = B * T * Fo; g.Tout = T; g.Fo = Fo;
-    g.nseg = 2;
-    g.seg[0] = Seg{0, -1, -2 * Ci, KS * Ci, 0};
-    g.seg[1] = Seg{0, 0, -2 * Ci, KS * Ci, 0};
-    g.N = Co;
-    Builder::layout_segs(g);
     Builder::Coef coef = [=](int nn, int s, int j) -> int32_t {
       const int kw = s, kh = j / Ci, ci = j % Ci;
       return pe(Wc, (((int64_t)nn * Ci + ci) * KS + kh) * 2 + kw, 1);
     };
-    std::function<void(int, int32_t*)> bias = [=](int nn, int32_t* o) { o[0] = pe(bc, nn, 1); o[1] = 0; };
-    b.pack_weights(F, g, coef, nm, 100 + i, &bias);
-    const int64_t Rr = (int64_t)B * T * Fo;
-    ency[i] = b.ws(nm + ".y", Rr * Co, adt);
-    encz[i] = b.ws(nm + ".z", Rr * Co, adt);
-    enc_mi[i] = b.ws(nm + ".mi", 2 * Co, DT_F32);
-    const int nblk = (int)((g.M + kBM - 1) / kBM);
-    Ptr part = b.ws(nm + ".stat", (int64_t)nblk * 2 * g.Npad, DT_F32);
-    g.y = ency[i]; g.y_bstride = (int64_t)T * Fo * Co; g.y_tstride = Fo * Co; g.y_fstride = Co; g.y_off = 0;
-    g.stats = cfg.training ? part : b.none();
-    b.push(F, OP_RUNGEMM, 100 + i).g = g;
-    {
-      Op& op = b.push(F, OP_BN_FINALIZE, 100 + i);
-      op.bnf.part = part; op.bnf.mean_invstd = enc_mi[i];
-      op.bnf.running_mean = b.sptr(pp + ".1.running_mean"); op.bnf.running_var = b.sptr(pp + ".1.running_var");
-      op.bnf.nblk = cfg.training ? nblk : -1; op.bnf.C = Co; op.bnf.Cpad = g.Npad; op.bnf.count = (double)Rr;
-      op.bnf.eps = 1e-5f; op.bnf.momentum = 0.1f;
-      Op& oa = b.push(F, OP_BN_APPLY, 100 + i);
-      oa.bna.y = ency[i]; oa.bna.z = encz[i]; oa.bna.mean_invstd = enc_mi[i];
-      oa.bna.gamma = b.pptr(pp + ".1.weight"); oa.bna.beta = b.pptr(pp + ".1.bias"); oa.bna.slope = b.pptr(pp + ".2.weight");
-      oa.bna.R = Rr; oa.bna.C = Co; oa.bna.dt = adt;
-    }
-    enc[i].f[0] = g; enc[i].coef[0] = coef; enc[i].bias = bias; enc[i].C = Co; enc[i].Fq = Fo; enc[i].R = Rr;
-    prev = encz[i];
+    Builder::Bias bias = [=](int nn, int32_t* o) { o[0] = pe(bc, nn, 1); o[1] = 0; };
+    enc[i] = b.enc_conv(F, 100 + i, "enc" + std::to_string(i), pp, x, Fe[i], Fo, Co, coef, bias, true, false);
+    x = Builder::ActSrc{enc[i].z, (int64_t)T * Fo * Co, Fo * Co, 0, Co};
   }
 
   // ---- single-layer LSTM + Linear (models.py:391-398, 483-486); feature order c*D + d
@@ -2122,10 +2108,10 @@ Plan* build_crn_plan(const ModelConfig& cfg) {
   Ptr cbuf = b.ws("lstm.c", BT * H, DT_F32);
   RunGemm ggx = Builder::gemm0();
   Builder::Coef cgx;
-  std::function<void(int, int32_t*)> bgx = [=](int nn, int32_t* o) { o[0] = pe(bih, gate_torch_row(nn, H), 1); o[1] = pe(bhh, gate_torch_row(nn, H), 1); };
+  Builder::Bias bgx = [=](int nn, int32_t* o) { o[0] = pe(bih, gate_torch_row(nn, H), 1); o[1] = pe(bhh, gate_torch_row(nn, H), 1); };
   {
     RunGemm& g = ggx;
-    g.x[0] = encz[n - 1]; g.xdt = adt; g.ydt = DT_F32;
+    g.x[0] = enc[n - 1].z; g.xdt = adt; g.ydt = DT_F32;
     g.bstride[0] = (int64_t)T * D * Cl; g.tstride[0] = D * Cl; g.rowlen[0] = D * Cl; g.Tin[0] = T;
     g.M = (int)BT; g.Tout = T; g.Fo = 1;
     g.nseg = D;
@@ -2147,7 +2133,7 @@ Plan* build_crn_plan(const ModelConfig& cfg) {
   Ptr decin = b.ws("decin", BT * D * Cl, adt);
   RunGemm proj = Builder::gemm0();
   Builder::Coef cproj;
-  std::function<void(int, int32_t*)> bproj;
+  Builder::Bias bproj;
   {
     const ParamInfo &Wt = b.par("tranform.weight"), &bt = b.par("tranform.bias");
     RunGemm& g = proj;
@@ -2165,9 +2151,7 @@ Plan* build_crn_plan(const ModelConfig& cfg) {
   }
 
   // ---- decoder (RealConvTranspose2d, tools_for_model.py:389-425; torch.cat([out, enc], 1) skips)
-  std::vector<Ptr> decy(n), decz(n), dec_mi(n);
-  struct DecSrc { Ptr p; int64_t bstride; int tstride, base, C; };
-  DecSrc dprev{decin, (int64_t)T * D * Cl, D * Cl, 0, Cl};
+  std::array<Builder::ActSrc, 2> src{Builder::ActSrc{decin, (int64_t)T * D * Cl, D * Cl, 0, Cl}, Builder::ActSrc{}};
   for (int d = 0; d < n; ++d) {
     const int idx = n - d;
     const int C0 = ch[idx], C1 = cfg.skip ? ch[idx] : 0, Co = ch[idx - 1];
@@ -2176,92 +2160,40 @@ Plan* build_crn_plan(const ModelConfig& cfg) {
     const std::string nm = "dec" + std::to_string(d);
     const std::string pp = "decoder." + std::to_string(d);
     const ParamInfo &Wc = b.par(pp + ".0.conv.weight"), &bc = b.par(pp + ".0.conv.bias");
-    const int64_t Rr = (int64_t)B * (T + 1) * Fo;
-    decy[d] = b.ws(nm + ".y", Rr * Co, adt);
-    if (!last) { decz[d] = b.ws(nm + ".z", Rr * Co, adt); dec_mi[d] = b.ws(nm + ".mi", 2 * Co, DT_F32); }
-    std::function<int32_t(int, int, int, int, int)> wcoef = [=](int nn, int s, int cc, int kh, int kw) -> int32_t {
+    Builder::ConvLayer& Ly = dec[d];
+    Ly.C = Co; Ly.Fq = Fo; Ly.R = (int64_t)B * (T + 1) * Fo;
+    Ly.y = b.ws(nm + ".y", Ly.R * Co, adt);
+    if (!last) { Ly.z = b.ws(nm + ".z", Ly.R * Co, adt); Ly.mi = b.ws(nm + ".mi", 2 * Co, DT_F32); }
+    Builder::WCoef wcoef = [=](int nn, int s, int cc, int kh, int kw) -> int32_t {
       const int rc = s == 0 ? cc : C0 + cc;
       return pe(Wc, (((int64_t)rc * Co + nn) * KS + kh) * 2 + kw, 1);
     };
-    std::function<void(int, int32_t*)> bias = [=](int nn, int32_t* o) { o[0] = pe(bc, nn, 1); o[1] = 0; };
+    Ly.bias = [=](int nn, int32_t* o) { o[0] = pe(bc, nn, 1); o[1] = 0; };
     const int nblk1 = (int)(((int64_t)B * (T + 1) * Fi + kBM - 1) / kBM);
-    Ptr part = b.none();
     const int npad_stat = (int)rup(Co, bn_of(Co));
-    if (!last) part = b.ws(nm + ".stat", (int64_t)2 * nblk1 * 2 * npad_stat, DT_F32);
-    for (int par = 0; par < 2; ++par) {
-      RunGemm g = Builder::gemm0();
-      g.xdt = adt; g.ydt = adt;
-      const int nsrc = cfg.skip ? 2 : 1;
-      DecSrc src[2] = {dprev, DecSrc{encz[idx - 1], (int64_t)T * Fi * C1, Fi * C1, 0, C1}};
-      g.nseg = 0;
-      const int ntap = par == 0 ? 3 : 2;
-      for (int s = 0; s < nsrc; ++s) {
-        g.x[s] = src[s].p; g.bstride[s] = src[s].bstride; g.tstride[s] = src[s].tstride; g.base[s] = src[s].base;
-        g.rowlen[s] = Fi * src[s].C; g.fstride[s] = src[s].C; g.Tin[s] = T;
-        for (int kw = 0; kw < 2; ++kw) g.seg[g.nseg++] = Seg{s, -kw, par == 0 ? -src[s].C : 0, ntap * src[s].C, 0};
-      }
-      g.M = B * (T + 1) * Fi; g.Tout = T + 1; g.Fo = Fi;
-      g.N = Co;
-      Builder::layout_segs(g);
-      const int c0 = C0, c1 = C1;
-      Builder::Coef coef = [=](int nn, int sg, int j) -> int32_t {
-        const int s = sg / 2, kw = sg % 2;
-        const int Cs = s == 0 ? c0 : c1;
-        const int jj = j / Cs, cc = j % Cs;
-        return wcoef(nn, s, cc, par == 0 ? 4 - 2 * jj : 3 - 2 * jj, kw);
-      };
-      b.pack_weights(F, g, coef, nm + ".p" + std::to_string(par), 400 + d, par == 0 ? &bias : nullptr);
-      if (par == 1) g.bias = dec[d].f[0].bias;
-      g.y = decy[d]; g.y_bstride = (int64_t)(T + 1) * Fo * Co; g.y_tstride = Fo * Co; g.y_fstride = 2 * Co; g.y_off = par * Co;
-      if (!last && cfg.training) g.stats = b.mk(A_WS, part.off + (int64_t)par * nblk1 * 2 * g.Npad * 4);
-      b.push(F, OP_RUNGEMM, 400 + d).g = g;
-      dec[d].f[par] = g; dec[d].coef[par] = coef;
-    }
-    dec[d].bias = bias; dec[d].C = Co; dec[d].Fq = Fo; dec[d].R = Rr;
+    Ptr part = last ? b.none() : b.ws(nm + ".stat", (int64_t)2 * nblk1 * 2 * npad_stat, DT_F32);
+    src[1] = Builder::ActSrc{enc[idx - 1].z, (int64_t)T * Fi * C1, Fi * C1, 0, C1};
+    b.dec_phases(F, 400 + d, nm, Ly, src, Fi, Co, wcoef, !last && cfg.training ? part : b.none(), nblk1, true);
     if (!last) {
-      Op& op = b.push(F, OP_BN_FINALIZE, 400 + d);
-      op.bnf.part = part; op.bnf.mean_invstd = dec_mi[d];
-      op.bnf.running_mean = b.sptr(pp + ".1.running_mean"); op.bnf.running_var = b.sptr(pp + ".1.running_var");
-      op.bnf.nblk = cfg.training ? 2 * nblk1 : -1; op.bnf.C = Co; op.bnf.Cpad = npad_stat; op.bnf.count = (double)Rr;
-      op.bnf.eps = 1e-5f; op.bnf.momentum = 0.1f;
-      Op& oa = b.push(F, OP_BN_APPLY, 400 + d);
-      oa.bna.y = decy[d]; oa.bna.z = decz[d]; oa.bna.mean_invstd = dec_mi[d];
-      oa.bna.gamma = b.pptr(pp + ".1.weight"); oa.bna.beta = b.pptr(pp + ".1.bias"); oa.bna.slope = b.pptr(pp + ".2.weight");
-      oa.bna.R = Rr; oa.bna.C = Co; oa.bna.dt = adt;
-      dprev = DecSrc{decz[d], (int64_t)(T + 1) * Fo * Co, Fo * Co, Fo * Co, Co};
+      b.bn_fwd(F, 400 + d, pp, Ly, part, 2 * nblk1, npad_stat, 0, 0);
+      src[0] = Builder::ActSrc{Ly.z, (int64_t)(T + 1) * Fo * Co, Fo * Co, Fo * Co, Co};   // frames 1..T of the T+1 buffer
     }
   }
 
   // ---- mask, iSTFT, outputs (models.py:519-532)
   Ptr est = b.ws("est", BT * SW, DT_F32);
   Ptr estm = b.ws("estm", BT * NF, DT_F32);
-  Ptr frames = b.ws("frames", BT * W, DT_F32);
+  Ptr frames = b.ws("frames", BT * b.fe.W, DT_F32);
   Mask mk;
   std::memset(&mk, 0, sizeof(mk));
   {
     const int Fo = Fe[0];
-    mk.spec = spec; mk.mask = decy[n - 1]; mk.est = est; mk.estm = estm; mk.dest = mk.dmask = mk.destm = b.none();
+    mk.spec = spec; mk.mask = dec[n - 1].y; mk.est = est; mk.estm = estm; mk.dest = mk.dmask = mk.destm = b.none();
     mk.frames = BT; mk.NF = NF; mk.mode = direct ? 5 : 3; mk.mdt = adt; mk.mch = 1;
     mk.mask_fstride = Fo; mk.mask_bstride = (int64_t)(T + 1) * Fo; mk.mask_base = Fo; mk.T = T;
     b.push(F, OP_MASK_FWD, 500).mask = mk;
   }
-  if (!b.istft_fft(F, 501, est, frames, BT, NFFT, win)) {
-    RunGemm g = Builder::gemm0();
-    g.x[0] = est; g.xdt = DT_F32; g.ydt = DT_F32;
-    g.bstride[0] = (int64_t)T * SW; g.tstride[0] = SW; g.rowlen[0] = SW; g.Tin[0] = T;
-    g.M = (int)BT; g.Tout = T; g.Fo = 1;
-    g.nseg = 1; g.seg[0] = Seg{0, 0, 0, SW, 0};
-    g.N = W;
-    Builder::layout_segs(g);
-    const_weights(g, [&](int nn, int j) { return j < 2 ? 0.0 : Kinv[((size_t)(j & 1) * NF + (j / 2 - 1)) * W + nn]; });
-    g.y = frames; g.y_bstride = (int64_t)T * W; g.y_tstride = W;
-    b.push(F, OP_RUNGEMM, 501).g = g;
-  }
-  Ola ola;
-  std::memset(&ola, 0, sizeof(ola));
-  ola.frames = frames; ola.wav = io_out; ola.coff = c_coff; ola.dwav = ola.dpad = b.none();
-  ola.B = B; ola.T = T; ola.L = L; ola.win = W; ola.hop = hop; ola.trim = trim;
-  b.push(F, OP_OLA_FWD, 502).ola = ola;
+  const Ola ola = b.istft_ola(F, est, frames, io_out);
   {
     SpecOut so;
     std::memset(&so, 0, sizeof(so));
@@ -2273,38 +2205,8 @@ Plan* build_crn_plan(const ModelConfig& cfg) {
 
   // =================================================================================================== backward
   if (cfg.training) {
-    Ptr dpad = b.ws("dpad", (int64_t)B * Lp, DT_F32);
-    Ptr dest = b.ws("dest", BT * SW, DT_F32);
-    {
-      Ola o = ola;
-      o.dwav = io_gw; o.dpad = dpad;
-      b.push(R, OP_OLA_BWD, 502).ola = o;
-      if (!b.istft_bwd_fft(R, 501, dpad, dest, B, Lp, T, hop, NFFT, win)) {
-        RunGemm g = Builder::gemm0();
-        g.x[0] = dpad; g.xdt = DT_F32; g.ydt = DT_F32;
-        g.bstride[0] = Lp; g.rowlen[0] = Lp; g.fstride[0] = hop; g.Tin[0] = 1;
-        g.M = (int)BT; g.Tout = 1; g.Fo = T;
-        g.nseg = 1; g.seg[0] = Seg{0, 0, 0, W, 0};
-        g.N = SW;
-        Builder::layout_segs(g);
-        const_weights(g, [&](int nn, int j) { return nn < 2 ? 0.0 : Kinv[((size_t)(nn & 1) * NF + (nn / 2 - 1)) * W + j]; });
-        g.y = dest; g.y_bstride = (int64_t)T * SW; g.y_fstride = SW;
-        b.push(R, OP_RUNGEMM, 501).g = g;
-      }
-    }
-    std::vector<Ptr> d_decy(n), d_decz(n), d_skip(n), d_encz(n), d_ency(n);
-    for (int d = 0; d < n; ++d) {
-      const int idx = n - d;
-      const int Co = ch[idx - 1], Fo = 2 * Fe[idx];
-      d_decy[d] = b.ws("dec" + std::to_string(d) + ".dy", (int64_t)B * (T + 1) * Fo * Co, adt);
-      if (idx != 1) d_decz[d] = b.ws("dec" + std::to_string(d) + ".dz", (int64_t)B * T * Fo * Co, adt);
-    }
-    for (int i = 0; i < n; ++i) {
-      const int64_t e = (int64_t)B * T * Fe[i + 1] * ch[i + 1];
-      d_ency[i] = b.ws("enc" + std::to_string(i) + ".dy", e, adt);
-      d_encz[i] = b.ws("enc" + std::to_string(i) + ".dz", e, adt);
-      if (cfg.skip) d_skip[i] = b.ws("enc" + std::to_string(i) + ".dskip", e, adt);
-    }
+    Ptr dest = b.istft_ola_bwd(R, ola, io_gw);
+    b.conv_grads(enc, dec, ch[0]);
     Ptr d_decin = b.ws("decin.d", BT * D * Cl, adt);
     {
       Ptr d_estm = b.ws("destm", BT * NF, DT_F32);       // io.grad_real [B][NF][T] -> [B*T][NF]
@@ -2313,62 +2215,24 @@ Plan* build_crn_plan(const ModelConfig& cfg) {
       s2.est = d_estm; s2.out_real = io_gr; s2.out_imag = b.none(); s2.B = B; s2.T = T; s2.NF = NF; s2.mode = 2;
       b.push(R, OP_SPECOUT_BWD, 503).so = s2;
       Mask m2 = mk;
-      m2.dest = dest; m2.dmask = d_decy[n - 1]; m2.destm = d_estm;
+      m2.dest = dest; m2.dmask = dec[n - 1].dy; m2.destm = d_estm;
       b.push(R, OP_MASK_BWD, 500).mask = m2;
     }
-    auto bn_bwd = [&](int tag, Ptr y, Ptr dz0, Ptr dz1, Ptr mi, const std::string& pp, int C, int64_t Rr, int64_t rpb, int skip, Ptr dy,
-                      const std::string& nm) {
-      int64_t rpbk = std::max<int64_t>(64, (Rr + 2047) / 2048);
-      const int nblk = (int)((Rr + rpbk - 1) / rpbk);
-      BnBwdReduce r;
-      std::memset(&r, 0, sizeof(r));
-      r.y = y; r.dz0 = dz0; r.dz1 = dz1; r.mean_invstd = mi;
-      r.gamma = b.pptr(pp + ".1.weight"); r.beta = b.pptr(pp + ".1.bias"); r.slope = b.pptr(pp + ".2.weight");
-      r.part = b.ws(nm + ".bnpart", (int64_t)nblk * 3 * C, DT_F32);
-      r.R = Rr; r.C = C; r.dt = adt; r.nblk = nblk; r.rows_per_blk = (int)rpbk; r.rpb = rpb; r.skip = skip;
-      b.push(R, OP_BN_BWD_REDUCE, tag).bnr = r;
-      BnBwdApply a;
-      std::memset(&a, 0, sizeof(a));
-      a.r = r; a.totals = b.ws(nm + ".bntot", 3 * C, DT_F32); a.dy = dy;
-      a.dgamma = b.pptr(pp + ".1.weight", A_GRAD); a.dbeta = b.pptr(pp + ".1.bias", A_GRAD); a.dslope = b.pptr(pp + ".2.weight", A_GRAD);
-      a.count = (double)Rr;
-      b.push(R, OP_BN_BWD_FINALIZE, tag).bnb = a;
-      b.push(R, OP_BN_BWD_APPLY, tag).bnb = a;
-    };
     for (int d = n - 1; d >= 0; --d) {
       const int idx = n - d;
-      const int C0 = ch[idx], C1 = cfg.skip ? ch[idx] : 0, Co = ch[idx - 1];
-      const int Fi = Fe[idx], Fo = 2 * Fi;
-      const bool last = (idx == 1);
+      const int C0 = ch[idx], C1 = cfg.skip ? ch[idx] : 0;
       const std::string nm = "dec" + std::to_string(d);
-      const std::string pp = "decoder." + std::to_string(d);
-      if (!last)
-        bn_bwd(400 + d, decy[d], d_decz[d], b.none(), dec_mi[d], pp, Co, dec[d].R, (int64_t)(T + 1) * Fo, Fo, d_decy[d], nm);
+      Builder::ConvLayer& Ly = dec[d];
+      if (idx != 1)
+        b.bn_bwd(R, 400 + d, Ly.y, Ly.dz, b.none(), Ly.mi, "decoder." + std::to_string(d), Ly.C, Ly.R, (int64_t)(T + 1) * Ly.Fq, Ly.Fq, Ly.dy, nm,
+                 false, nullptr, false);
       b.cur_lane = 1;                           // weight gradients of the decoder: nothing downstream needs them before UNPACK
-      for (int par = 0; par < 2; ++par) b.wgrad(R, dec[d].f[par], d_decy[d], dec[d].coef[par], 400 + d, &dec[d].bias);
+      for (int par = 0; par < 2; ++par) b.wgrad(R, Ly.f[par], Ly.dy, Ly.coef[par], 400 + d, &Ly.bias);
       b.cur_lane = 0;
-      const int nsrc = cfg.skip ? 2 : 1;
-      for (int s = 0; s < nsrc; ++s) {
-        const int Cs = s == 0 ? C0 : C1;
-        RunGemm g = Builder::gemm0();
-        g.x[0] = d_decy[d]; g.xdt = adt; g.ydt = adt;
-        g.bstride[0] = (int64_t)(T + 1) * Fo * Co; g.tstride[0] = Fo * Co; g.rowlen[0] = Fo * Co; g.fstride[0] = 2 * Co; g.Tin[0] = T + 1;
-        g.M = B * T * Fi; g.Tout = T; g.Fo = Fi;
-        g.nseg = 2;
-        g.seg[0] = Seg{0, 0, -2 * Co, KS * Co, 0};
-        g.seg[1] = Seg{0, 1, -2 * Co, KS * Co, 0};
-        g.N = Cs;
-        Builder::layout_segs(g);
-        const Builder::Coef f0 = dec[d].coef[0], f1 = dec[d].coef[1];
-        Builder::Coef coef = [=](int nn, int sg, int j) -> int32_t {
-          const int kw = sg, kh = j / Co, co = j % Co;
-          const int par = kh & 1;
-          const int jj = par == 0 ? (4 - kh) / 2 : (3 - kh) / 2;
-          return (par == 0 ? f0 : f1)(co, s * 2 + kw, jj * Cs + nn);
-        };
-        b.pack_weights(R, g, coef, nm + ".dg" + std::to_string(s), 400 + d);
-        g.y = s == 0 ? (d > 0 ? d_decz[d - 1] : d_decin) : d_skip[idx - 1];
-        g.y_bstride = (int64_t)T * Fi * Cs; g.y_tstride = Fi * Cs; g.y_fstride = Cs; g.y_off = 0;
+      for (int s = 0; s < (cfg.skip ? 2 : 1); ++s) {
+        Builder::Coef coef;
+        const RunGemm g = b.dec_dgrad(R, 400 + d, nm, Ly, Ly.C, Fe[idx], s, s == 0 ? C0 : C1, s == 0 ? (d > 0 ? dec[d - 1].dz : d_decin) : enc[idx - 1].dskip,
+                                      coef, true);
         b.push(R, OP_RUNGEMM, 400 + d).g = g;
       }
     }
@@ -2421,47 +2285,24 @@ Plan* build_crn_plan(const ModelConfig& cfg) {
         const Builder::Coef cf = cgx;
         Builder::Coef coef = [=](int nn, int sg, int j) -> int32_t { return cf(j, q, nn); };
         b.pack_weights(R, g, coef, "lstm.dx" + std::to_string(q), 200);
-        g.y = d_encz[n - 1]; g.y_bstride = (int64_t)T * D * Cl; g.y_tstride = D * Cl; g.y_off = q * Cl;
+        g.y = enc[n - 1].dz; g.y_bstride = (int64_t)T * D * Cl; g.y_tstride = D * Cl; g.y_off = q * Cl;
         b.push(R, OP_RUNGEMM, 200).g = g;
       }
     }
     for (int i = n - 1; i >= 0; --i) {
-      const int Ci = ch[i], Co = ch[i + 1], Fi = Fe[i], Fo = Fe[i + 1];
       const std::string nm = "enc" + std::to_string(i);
-      const std::string pp = "encoder." + std::to_string(i);
-      bn_bwd(100 + i, ency[i], d_encz[i], cfg.skip ? d_skip[i] : b.none(), enc_mi[i], pp, Co, enc[i].R, (int64_t)T * Fo, 0, d_ency[i], nm);
-      b.wgrad(R, enc[i].f[0], d_ency[i], enc[i].coef[0], 100 + i, &enc[i].bias);
-      if (i == 0) continue;
-      for (int par = 0; par < 2; ++par) {
-        RunGemm g = Builder::gemm0();
-        g.x[0] = d_ency[i]; g.xdt = adt; g.ydt = adt;
-        g.bstride[0] = (int64_t)T * Fo * Co; g.tstride[0] = Fo * Co; g.rowlen[0] = Fo * Co; g.fstride[0] = Co; g.Tin[0] = T;
-        g.M = B * T * Fo; g.Tout = T; g.Fo = Fo;
-        const int ntap = par == 0 ? 3 : 2;
-        g.nseg = 2;
-        g.seg[0] = Seg{0, 1, par == 0 ? -Co : 0, ntap * Co, 0};
-        g.seg[1] = Seg{0, 0, par == 0 ? -Co : 0, ntap * Co, 0};
-        g.N = Ci;
-        Builder::layout_segs(g);
-        const Builder::Coef cf = enc[i].coef[0];
-        Builder::Coef coef = [=](int nn, int sg, int j) -> int32_t {
-          const int kw = sg, jj = j / Co, co = j % Co;
-          return cf(co, kw, (par == 0 ? 4 - 2 * jj : 3 - 2 * jj) * Ci + nn);
-        };
-        b.pack_weights(R, g, coef, nm + ".dg" + std::to_string(par), 100 + i);
-        g.y = d_encz[i - 1]; g.y_bstride = (int64_t)T * Fi * Ci; g.y_tstride = Fi * Ci; g.y_fstride = 2 * Ci; g.y_off = par * Ci;
+      Builder::ConvLayer& Ly = enc[i];
+      b.bn_bwd(R, 100 + i, Ly.y, Ly.dz, cfg.skip ? Ly.dskip : b.none(), Ly.mi, "encoder." + std::to_string(i), Ly.C, Ly.R, (int64_t)T * Ly.Fq, 0,
+               Ly.dy, nm, false, nullptr, false);
+      b.wgrad(R, Ly.f[0], Ly.dy, Ly.coef[0], 100 + i, &Ly.bias);
+      for (int par = 0; i > 0 && par < 2; ++par) {
+        const RunGemm g = b.enc_dgrad(R, 100 + i, nm, Ly, ch[i], Fe[i], par, enc[i - 1].dz);
         b.push(R, OP_RUNGEMM, 100 + i).g = g;
       }
     }
     b.finish_unpack(R);
   }
-  finalize_rungemms(b, P);
-  P->arena_bytes[A_WS] = b.ws_off;
-  P->arena_bytes[A_PARAM] = nparam * 4;
-  P->arena_bytes[A_GRAD] = nparam * 4;
-  P->arena_bytes[A_STATE] = std::max<int64_t>(nstate, 1) * 4;
-  P->arena_bytes[A_CONST] = (int64_t)P->consts.size();
-  P->arena_bytes[A_IO] = b.io_off;
+  finish_plan(b, P, nparam, nstate);
   return P;
 }
 
@@ -2474,47 +2315,20 @@ Plan* build_frontend_plan(const ModelConfig& cfg) {
   Builder b;
   b.P = P;
   b.c = cfg;
-  const int B = cfg.B, L = cfg.L, W = cfg.win_len, hop = cfg.hop, NFFT = cfg.fft_len;
-  const int trim = W - hop;
-  const int T = (L + 2 * trim - W) / hop + 1;
-  const int NF = NFFT / 2 + 1, NS = NF + 1, SW = NS * 2;
+  b.fe = Stft(cfg);
+  const int B = cfg.B, T = b.fe.T, NF = b.fe.NF;
   P->T = T;
   P->NF = NF;
-  Ptr io_wav = b.io("wav", (int64_t)B * L);
+  Ptr io_wav = b.io("wav", (int64_t)B * cfg.L);
   Ptr io_or = b.io("out_real", (int64_t)B * NF * T);
   Ptr io_oi = b.io("out_imag", (int64_t)B * NF * T);
-  std::vector<double> win(W);
-  for (int j = 0; j < W; ++j) win[j] = window_value(cfg, j, W);    // win_type None: np.ones (tools_for_model.py:17-18)
-  Ptr spec = b.ws("spec", (int64_t)B * T * SW, DT_F32);
-  if (!b.stft_fft(P->fwd, 1, io_wav, spec, B, L, T, hop, trim, NFFT, win)) {
-  RunGemm g = Builder::gemm0();
-  g.x[0] = io_wav; g.xdt = DT_F32; g.ydt = DT_F32;
-  g.bstride[0] = L; g.rowlen[0] = L; g.fstride[0] = hop; g.Tin[0] = 1;
-  g.M = B * T; g.Tout = 1; g.Fo = T;
-  g.nseg = 1; g.seg[0] = Seg{0, 0, -trim, W, 0};
-  g.N = SW;
-  Builder::layout_segs(g);
-  {
-    std::vector<float> wt((size_t)g.Npad * g.ldw, 0.f);
-    for (int nn = 2; nn < g.N; ++nn)
-      for (int j = 0; j < W; ++j) {
-        const double ang = 2.0 * kPi * (double)(((int64_t)(nn / 2 - 1) * j) % NFFT) / NFFT;
-        wt[(size_t)nn * g.ldw + j] = (float)(((nn & 1) == 0 ? std::cos(ang) : -std::sin(ang)) * win[j]);
-      }
-    g.w = b.cst(wt.data(), (int64_t)wt.size() * 4);
-  }
-  g.y = spec; g.y_bstride = (int64_t)T * SW; g.y_fstride = SW;
-  b.push(P->fwd, OP_RUNGEMM, 1).g = g;
-  }
+  Ptr spec = b.ws("spec", (int64_t)B * T * b.fe.SW, DT_F32);
+  b.stft_fwd(P->fwd, 1, io_wav, spec);
   SpecOut so;
   std::memset(&so, 0, sizeof(so));
   so.est = spec; so.out_real = io_or; so.out_imag = io_oi; so.B = B; so.T = T; so.NF = NF;
   b.push(P->fwd, OP_SPECOUT_FWD, 2).so = so;
-  finalize_rungemms(b, P);
-  P->arena_bytes[A_WS] = b.ws_off;
-  P->arena_bytes[A_PARAM] = 4; P->arena_bytes[A_GRAD] = 4; P->arena_bytes[A_STATE] = 4;
-  P->arena_bytes[A_CONST] = (int64_t)P->consts.size();
-  P->arena_bytes[A_IO] = b.io_off;
+  finish_plan(b, P, 0, 0);
   return P;
 }
 
@@ -3001,15 +2815,9 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
     }
     b.finish_unpack(R);
   }
-  finalize_rungemms(b, P);
+  finish_plan(b, P, nparam, 0);
   for (size_t k = 0; k < P->bwd.size(); ++k)
     if (P->bwd[k].kind == OP_UNPACK && P->bwd[k].tag == 998) P->bucket_op = (int32_t)k;
-  P->arena_bytes[A_WS] = b.ws_off;
-  P->arena_bytes[A_PARAM] = nparam * 4;
-  P->arena_bytes[A_GRAD] = nparam * 4;
-  P->arena_bytes[A_STATE] = 4;
-  P->arena_bytes[A_CONST] = (int64_t)P->consts.size();
-  P->arena_bytes[A_IO] = b.io_off;
   return P;
 }
 
@@ -3059,11 +2867,7 @@ Plan* build_torchstft_plan(const ModelConfig& cfg) {
   std::memset(&so, 0, sizeof(so));
   so.est = spec; so.out_real = io_spec; so.out_imag = b.none(); so.B = B; so.T = T; so.NF = NF; so.mode = 3;
   b.push(P->fwd, OP_SPECOUT_FWD, 3).so = so;
-  finalize_rungemms(b, P);
-  P->arena_bytes[A_WS] = b.ws_off;
-  P->arena_bytes[A_PARAM] = 4; P->arena_bytes[A_GRAD] = 4; P->arena_bytes[A_STATE] = 4;
-  P->arena_bytes[A_CONST] = (int64_t)P->consts.size();
-  P->arena_bytes[A_IO] = b.io_off;
+  finish_plan(b, P, 0, 0);
   return P;
 }
 
@@ -3118,11 +2922,7 @@ Plan* build_torchistft_plan(const ModelConfig& cfg) {
   ola.frames = frames; ola.wav = io_wav; ola.coff = b.cst(env.data(), (int64_t)env.size() * 4); ola.dwav = ola.dpad = b.none();
   ola.B = B; ola.T = T; ola.L = L; ola.win = NFFT; ola.hop = hop; ola.trim = pad; ola.noclamp = 1;
   b.push(P->fwd, OP_OLA_FWD, 4).ola = ola;
-  finalize_rungemms(b, P);
-  P->arena_bytes[A_WS] = b.ws_off;
-  P->arena_bytes[A_PARAM] = 4; P->arena_bytes[A_GRAD] = 4; P->arena_bytes[A_STATE] = 4;
-  P->arena_bytes[A_CONST] = (int64_t)P->consts.size();
-  P->arena_bytes[A_IO] = b.io_off;
+  finish_plan(b, P, 0, 0);
   return P;
 }
 
