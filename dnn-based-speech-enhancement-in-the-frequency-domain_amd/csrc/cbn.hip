@@ -5,6 +5,8 @@
 // Forward:   STATS    y -> per-block sums of xr, xi, xr^2, xi^2, xr xi                                  (one read of y)
 //            FINALIZE sums -> M, V (+eps), U = V^-1/2, Z = W U, b' = B - Z M; running statistics lerp    (fp64, one workgroup per complex channel)
 //            APPLY    z = prelu(Z x + b')                                                              (read y, write z)
+// SyncBN (bn_world > 1): each FINALIZE runs twice around an all-reduce of fp64 totals, as BatchNorm's does (BnFinalize::mode): mode 1 publishes
+// this rank's sums (the backward's also writes this rank's parameter gradients), mode 2 finishes from the sums of all ranks.
 // Backward:  with dbn = prelu'(bn) dz (bn recomputed from y), x~ = x - M, N rows:
 //            REDUCE   per-block sums of dbn (2), dbn x~^T (4), slope gradient share
 //            FINALIZE dB = sum dbn; dZ = sum dbn x~^T; dW = dZ U (symmetric W: the two off-diagonal entries add); dU = W dZ (symmetric U likewise);
@@ -145,8 +147,19 @@ __global__ __launch_bounds__(256) void cbn_finalize_kernel(const CbnFwd d, const
   float* rv1 = d.RV[1].arena >= 0 ? reinterpret_cast<float*>(rp(ab, d.RV[1])) : nullptr;
   float* rv2 = d.RV[2].arena >= 0 ? reinterpret_cast<float*>(rp(ab, d.RV[2])) : nullptr;
   if (d.training) {
-    block_totals<5>(reinterpret_cast<const float*>(rp(ab, d.part)), d.nblk, 5 * h, h, k, tot);
-    if (threadIdx.x != 0) return;
+    if (d.mode == 2) {                           // SyncBN: the totals of all ranks are already in place
+      if (threadIdx.x != 0) return;
+      const double* st = reinterpret_cast<const double*>(rp(ab, d.totals));
+      for (int j = 0; j < 5; ++j) tot[j] = st[j * h + k];
+    } else {
+      block_totals<5>(reinterpret_cast<const float*>(rp(ab, d.part)), d.nblk, 5 * h, h, k, tot);
+      if (threadIdx.x != 0) return;
+      if (d.mode == 1) {                         // SyncBN: publish this rank's sums, the caller all-reduces them
+        double* st = reinterpret_cast<double*>(rp(ab, d.totals));
+        for (int j = 0; j < 5; ++j) st[j * h + k] = tot[j];
+        return;
+      }
+    }
     mr = tot[0] / d.count; mi = tot[1] / d.count;
     vrr = tot[2] / d.count - mr * mr; vii = tot[3] / d.count - mi * mi; vri = tot[4] / d.count - mr * mi;
     if (vrr < 0) vrr = 0;
@@ -265,8 +278,14 @@ __global__ __launch_bounds__(256) void cbn_bwd_finalize_kernel(const CbnBwd d, c
   const int k = blockIdx.x, h = d.C / 2;
   __shared__ double tot[7];
   const float* part = reinterpret_cast<const float*>(rp(ab, d.part));
-  block_totals<6>(part, d.nblk, 7 * h, h, k, tot);
-  if (k == 0) {                                  // the PReLU slope gradient is one scalar: block 0 adds the shares of all blocks (column 0 of row 6)
+  if (d.mode == 2) {                             // SyncBN: the totals of all ranks are in place; mode 1 wrote the parameter gradients
+    if (threadIdx.x != 0) return;
+    const double* st = reinterpret_cast<const double*>(rp(ab, d.totals));
+    for (int j = 0; j < 6; ++j) tot[j] = st[j * h + k];
+  } else {
+    block_totals<6>(part, d.nblk, 7 * h, h, k, tot);
+  }
+  if (d.mode != 2 && k == 0) {                   // the PReLU slope gradient is one scalar: block 0 adds the shares of all blocks (column 0 of row 6)
     __shared__ double rs[256];
     double sa = 0.0;
     for (int b = threadIdx.x; b < d.nblk; b += 256) sa += part[(int64_t)b * 7 * h + 6 * h];
@@ -282,11 +301,19 @@ __global__ __launch_bounds__(256) void cbn_bwd_finalize_kernel(const CbnBwd d, c
   const double urr = coef[8 * h + k], uri = coef[9 * h + k], uii = coef[10 * h + k];
   const double wrr = reinterpret_cast<const float*>(rp(ab, d.W[0]))[k], wri = reinterpret_cast<const float*>(rp(ab, d.W[1]))[k],
                wii = reinterpret_cast<const float*>(rp(ab, d.W[2]))[k];
-  reinterpret_cast<float*>(rp(ab, d.dB[0]))[k] = (float)dbr;
-  reinterpret_cast<float*>(rp(ab, d.dB[1]))[k] = (float)dbi;
-  reinterpret_cast<float*>(rp(ab, d.dW[0]))[k] = (float)(dzrr * urr + dzri * uri);
-  reinterpret_cast<float*>(rp(ab, d.dW[1]))[k] = (float)(dzrr * uri + dzri * uii + dzir * urr + dzii * uri);
-  reinterpret_cast<float*>(rp(ab, d.dW[2]))[k] = (float)(dzir * uri + dzii * uii);
+  if (d.mode != 2) {
+    // mode 1: this rank's share - dB and dW = dZ U are linear in the sums and U is global, so the gradient all-reduce completes them
+    reinterpret_cast<float*>(rp(ab, d.dB[0]))[k] = (float)dbr;
+    reinterpret_cast<float*>(rp(ab, d.dB[1]))[k] = (float)dbi;
+    reinterpret_cast<float*>(rp(ab, d.dW[0]))[k] = (float)(dzrr * urr + dzri * uri);
+    reinterpret_cast<float*>(rp(ab, d.dW[1]))[k] = (float)(dzrr * uri + dzri * uii + dzir * urr + dzii * uri);
+    reinterpret_cast<float*>(rp(ab, d.dW[2]))[k] = (float)(dzir * uri + dzii * uii);
+    if (d.mode == 1) {                           // SyncBN: publish this rank's sums, the caller all-reduces them
+      double* st = reinterpret_cast<double*>(rp(ab, d.totals));
+      for (int j = 0; j < 6; ++j) st[j * h + k] = tot[j];
+      return;
+    }
+  }
   // dU = W^T dZ with W = [[wrr, wri], [wri, wii]]; U is symmetric: its off-diagonal entry collects both positions
   const double durr = wrr * dzrr + wri * dzir, duii = wri * dzri + wii * dzii, duri = (wrr * dzri + wri * dzii) + (wri * dzrr + wii * dzir);
   // back through U(V + eps I): the forward scalars again from the saved covariance

@@ -857,7 +857,9 @@ void finalize_rungemms(Builder& b, Plan* P) {
   }
   // SyncBN (cfg.bn_world > 1): every training-mode BN_FINALIZE becomes "publish this rank's sums" + "statistics from the
   // all-reduced sums" with a sync point in between; every BN_BWD_FINALIZE is followed by a sync point on its totals.
-  // Counts become global: every descriptor that carries a BatchNorm count (BN_FINALIZE, BN_BWD_APPLY, the kRunDyFromBn WGRAD) is scaled here.
+  // ComplexBatchNorm: both CBN_FINALIZE and CBN_BWD_FINALIZE become such a pair around fp64 totals (5 and 6 sums per channel pair).
+  // Counts become global: every descriptor that carries a BatchNorm count (BN_FINALIZE, BN_BWD_APPLY, the kRunDyFromBn WGRAD) is scaled here;
+  // of the CBN descriptors only the finalize ops read theirs.
   // The caller (models.py / hostsim tests) runs the op ranges between sync points and all-reduces.
   const int world = P->cfg.bn_world;
   if (world > 1 && P->cfg.training) {
@@ -879,6 +881,15 @@ void finalize_rungemms(Builder& b, Plan* P) {
           P->syncs.push_back(SyncPoint{phase, (int32_t)out.size() - 1, op.bnb.totals, 2 * (int64_t)op.bnb.r.C, 0});
         } else if (op.kind == OP_BN_BWD_APPLY) {
           op.bnb.count *= world;
+          out.push_back(op);
+        } else if ((op.kind == OP_CBN_FINALIZE && op.cbf.training) || op.kind == OP_CBN_BWD_FINALIZE) {
+          const bool fwd = op.kind == OP_CBN_FINALIZE;
+          const int h = fwd ? op.cbf.C / 2 : op.cbb.C / 2, ns = fwd ? 5 : 6;
+          const Ptr tot = b.ws("syncbn.ctot" + std::to_string(k++), (int64_t)ns * h * 2, DT_F32);     // ns*h doubles
+          if (fwd) { op.cbf.totals = tot; op.cbf.mode = 1; } else { op.cbb.totals = tot; op.cbb.mode = 1; }
+          out.push_back(op);
+          P->syncs.push_back(SyncPoint{phase, (int32_t)out.size() - 1, tot, (int64_t)ns * h, 1});
+          if (fwd) { op.cbf.mode = 2; op.cbf.count *= world; } else { op.cbb.mode = 2; op.cbb.count *= world; }
           out.push_back(op);
         } else if (op.kind == OP_WGRAD && (op.g.flags & kRunDyFromBn)) {
           op.g.bnb_inv_count /= (float)world;       // the BatchNorm backward fused into enc0's weight gradient divides the all-reduced totals
@@ -946,7 +957,9 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
 
   // ------------------------------------------------------------------ parameters (reference registration order)
   const bool cbn = cfg.use_cbn != 0;
-  if (cbn && cfg.bn_world > 1) { P->error = "ComplexBatchNorm has no SyncBN plan"; return P; }
+  // SyncBN for ComplexBatchNorm is built on request (cbn_sync, which models.py sets for GradientExchange(sync_bn=True)); bn_world alone keeps
+  // refusing it, as it did before the CBN finalize kernels had their SyncBN modes
+  if (cbn && cfg.bn_world > 1 && !cfg.cbn_sync) { P->error = "ComplexBatchNorm SyncBN plans need cbn_sync = 1"; return P; }
   // the normalisation + PReLU behind a conv: nn.BatchNorm2d(C) or ComplexBatchNorm(C) (tools_for_model.py:441-467: 5 parameters and 5 buffers of C / 2)
   auto add_norm = [&](const std::string& p, int C) {
     if (cbn) {

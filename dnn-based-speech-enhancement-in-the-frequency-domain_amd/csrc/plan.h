@@ -25,7 +25,7 @@ struct ModelConfig {
   int32_t grad_buckets;     // 2: decoder + LSTM gradients unpacked before the encoder backward (DDP overlap)
   int32_t use_cbn;          // DCCRN: ComplexBatchNorm instead of BatchNorm2d
   int32_t window;           // 0 periodic Hann, 1 rectangular (ConvSTFT win_type None), 2 window_values
-  int32_t pad_;
+  int32_t cbn_sync;         // use_cbn with bn_world > 1: 1 builds the ComplexBatchNorm SyncBN plan; 0 refuses it
   const double* window_values;   // window == 2: win_len values (valid during build_plan only)
 };
 

@@ -192,9 +192,11 @@ struct CbnFwd {                // OP_CBN_STATS (y -> part), OP_CBN_FINALIZE (par
   Ptr W[3], Bv[2], slope;      // Wrr Wri Wii, Br Bi (A_PARAM), PReLU slope
   Ptr RM[2], RV[3];            // RMr RMi, RVrr RVri RVii (A_STATE)
   int64_t R;
-  int32_t C, dt, nblk, rows_per_blk, training, pad_;
-  double count;
+  int32_t C, dt, nblk, rows_per_blk, training, mode;   // FINALIZE mode as in BnFinalize: 0 part -> coef; SyncBN 1: part -> totals (this rank's
+                                                       // sums, no coef, no running update); 2: totals (all-reduced in between) -> coef
+  double count;                // rows contributing (all ranks in mode 2)
   float eps, momentum;
+  Ptr totals;                  // fp64 [5][h] (modes 1, 2)
 };
 struct CbnBwd {                // OP_CBN_BWD_REDUCE (-> part), OP_CBN_BWD_FINALIZE (part -> coefb, parameter gradients), OP_CBN_BWD_APPLY (-> dy)
   Ptr y, dz0, dz1, dy;         // dz0 / dz1 / rpb / skip as in BnBwdReduce
@@ -202,8 +204,10 @@ struct CbnBwd {                // OP_CBN_BWD_REDUCE (-> part), OP_CBN_BWD_FINALI
   Ptr W[3], slope;
   Ptr dW[3], dB[2], dslope;    // A_GRAD
   int64_t R, rpb;
-  int32_t C, dt, nblk, rows_per_blk, skip, pad_;
-  double count;
+  int32_t C, dt, nblk, rows_per_blk, skip, mode;       // FINALIZE mode 0: part -> coefb + parameter gradients; SyncBN 1: part -> parameter
+                                                       // gradients of this rank's rows + totals; 2: totals (all-reduced in between) -> coefb
+  double count;                // rows contributing (all ranks in mode 2)
+  Ptr totals;                  // fp64 [6][h] (modes 1, 2)
 };
 
 // LSTM recurrence (input GEMM hoisted).  G independent groups, group g uses weight set g % nset.

@@ -12,7 +12,8 @@ The reference has no distributed code at all; this is a new capab
   * averaging (1/world) is folded into the fused Adam kernel (grad_scale), no extra pass.
 BatchNorm statistics stay per rank by default (standard DDP semantics), which is what the throughput numbers
 use; `GradientExchange(sync_bn=True)` switches `train_step` to SyncBN plans (statistics over all ranks: N ranks x B/N
-utterances == the reference's single process with batch B; tests/test_ddp_gloo.py pins that with world size 2).
+utterances == the reference's single process with batch B, BatchNorm2d and ComplexBatchNorm alike; tests/test_ddp_gloo.py and
+tests/test_gpu_cbn_syncbn.py pin that with world size 2).
 """
 import os
 
@@ -73,7 +74,8 @@ class GradientExchange:
 
 
     def all_reduce_stats(self, t: torch.Tensor):
-        """SyncBN sync point: in-place sum of a per-channel statistics buffer (2*C values) over the ranks, ordered on the
+        """SyncBN sync point: in-place sum of a per-channel statistics buffer (BatchNorm: 2*C fp32 or fp64 values; ComplexBatchNorm: 5 or 6
+        fp64 values per channel pair) over the ranks, ordered on the
         current stream (torch's NCCL wrapper inserts the stream dependencies)."""
         if self.active:
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.pg)

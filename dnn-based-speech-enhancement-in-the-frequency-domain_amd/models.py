@@ -466,7 +466,8 @@ class DCCRN(_SefdModule):
         return Plan(B, L, kernel_num=tuple(self.kernel_num[1:]), rnn_layers=self.hidden_layers, rnn_units=self.rnn_units,
                     win_len=self.win_len, win_inc=self.win_inc, fft_len=self.fft_len, masking_mode=self.masking_mode,
                     lstm=self._lstm_kind, skip_type=self._skip, act_dtype=self.act_dtype, training=training, model="DCCRN",
-                    bn_world=getattr(self, "_bn_world", 1), grad_buckets=getattr(self, "_grad_buckets", 1), use_cbn=self.use_cbn, win_type=self.win_type)
+                    bn_world=getattr(self, "_bn_world", 1), grad_buckets=getattr(self, "_grad_buckets", 1), use_cbn=self.use_cbn, win_type=self.win_type,
+                    cbn_sync=getattr(self, "_bn_world", 1) > 1)
 
     # ---- reference surface ----------------------------------------------------------------------------------
     def forward(self, inputs, targets=0):

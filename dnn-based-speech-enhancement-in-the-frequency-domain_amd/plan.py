@@ -20,7 +20,8 @@ FSN_NORMS = {"offline_laplace_norm": 0, "cumulative_laplace_norm": 1, "offline_g
 class Plan:
     def __init__(self, B, L, kernel_num=(32, 64, 128, 256, 256, 256), rnn_layers=2, rnn_units=256, win_len=400,
                  win_inc=100, fft_len=512, masking_mode="E", lstm="complex", skip_type=True, act_dtype="fp32",
-                 kernel_size=5, training=True, model="DCCRN", fsn=None, bn_world=1, grad_buckets=1, use_cbn=False, win_type="hanning"):
+                 kernel_size=5, training=True, model="DCCRN", fsn=None, bn_world=1, grad_buckets=1, use_cbn=False, win_type="hanning",
+                 cbn_sync=False):
         self.lib = _lib.lib()
         if masking_mode not in MASK_MODES:
             raise NotImplementedError(f"masking_mode {masking_mode!r} is not on the HIP path yet")
@@ -51,6 +52,7 @@ class Plan:
         cfg.bn_world = int(bn_world)
         cfg.grad_buckets = int(grad_buckets)
         cfg.use_cbn = 1 if use_cbn else 0
+        cfg.cbn_sync = 1 if cbn_sync else 0        # use_cbn + bn_world > 1: SyncBN for ComplexBatchNorm is built on request only
         if win_type in (None, "None"):
             cfg.window = 1
         elif win_type in ("hanning", "hann"):

@@ -48,7 +48,7 @@ typedef struct sefd_model_config {
   int32_t use_cbn;        /* DCCRN(use_cbn=True) (models.py:25, 76, 120): ComplexBatchNorm (tools_for_model.py:430-607) instead of nn.BatchNorm2d */
   int32_t window;         /* ConvSTFT / ConviSTFT window (tools_for_model.py:17-20): 0 periodic Hann (cfg.window = 'hanning'), 1 rectangular (win_type None),
                              2 the table `window_values` (any other scipy.signal.get_window(name, win_len, fftbins=True): the host evaluates it) */
-  int32_t pad_;
+  int32_t cbn_sync;       /* use_cbn with bn_world > 1: 1 builds the ComplexBatchNorm SyncBN plan (fp64 sync points); 0 refuses it */
   const double* window_values;   /* window == 2: win_len doubles, read during sefd_plan_create only */
 } sefd_model_config;
 
