@@ -188,17 +188,18 @@ __global__ __launch_bounds__(64) void fsn_mean_kernel(const Fsn d, const ArenaBa
 
 __device__ __forceinline__ int reflect_idx(int f, int F) { return f < 0 ? -f : (f >= F ? 2 * (F - 1) - f : f); }
 
-// un-normalised sub-band input element (tools_for_model.py:806-837 + models.py:649-655), k < NB: neighbour f - n + k, k == NB: full band
+// un-normalised sub-band input element (tools_for_model.py:806-837 + models.py:649-655), k < NB: neighbour f - n + k of the magnitude,
+// k = NB + j: neighbour f - nf + j of the full-band output (nf = 0: the bin itself)
 __device__ __forceinline__ float sb_raw(const Fsn& d, const float* mt, const float* fbo, int t, int b, int f, int k) {
   const int n = (d.NB - 1) / 2;
   if (k < d.NB) return mt[((int64_t)t * d.B + b) * d.F + reflect_idx(f - n + k, d.F)];
-  return fbo[((int64_t)t * d.B + b) * d.FP + f];
+  return fbo[((int64_t)t * d.B + b) * d.FP + reflect_idx(f - (fsn_nfb(d) >> 1) + (k - d.NB), d.F)];
 }
 __global__ __launch_bounds__(256) void fsn_sbsum_kernel(const Fsn d, const ArenaBases ab) {    // grid (F, B): sums[b][f] over (k, t)
   const float* mt = reinterpret_cast<const float*>(rp(ab, d.in));
   const float* fbo = reinterpret_cast<const float*>(rp(ab, d.aux));
   float* sums = reinterpret_cast<float*>(rp(ab, d.sums));
-  const int f = blockIdx.x, b = blockIdx.y, W = d.NB + 1;
+  const int f = blockIdx.x, b = blockIdx.y, W = fsn_w(d);
   float s = 0.f;
   for (int i = threadIdx.x; i < d.TP * W; i += 256) s += sb_raw(d, mt, fbo, i / W, b, f, i % W);
   __shared__ float red[4];
@@ -211,9 +212,34 @@ __global__ __launch_bounds__(256) void fsn_sbbuild_kernel(const Fsn d, const Are
   const float* mt = reinterpret_cast<const float*>(rp(ab, d.in));
   const float* fbo = reinterpret_cast<const float*>(rp(ab, d.aux));
   const float* mu = reinterpret_cast<const float*>(rp(ab, d.sums));
-  char* out = rp(ab, d.out);                                            // [TP][B*F][NB+1]
-  const int W = d.NB + 1;
-  if (d.mode == 0 && d.dt == DT_BF16 && (W & 7) == 0 && (int64_t)d.TP * d.B * d.F * (W / 8) < (1LL << 31)) {
+  char* out = rp(ab, d.out);                                            // [TP][B*F][WP], columns W..WP-1 zero
+  const int W = fsn_w(d), WP = fsn_wp(d);
+  if (d.mode == 0 && d.dt == DT_BF16 && (int64_t)d.TP * d.B * d.F * (WP / 8) < (1LL << 31) && !(W == WP && fsn_nfb(d) == 1)) {
+    // any other width: the same 16-byte chunks over rows stored WP = roundup(W, 8) wide, the full-band window reflect-indexed, pad columns zero
+    const unsigned CH = (unsigned)WP / 8, n8 = (unsigned)d.TP * d.B * d.F * CH;
+    const int nn = (d.NB - 1) / 2, nf = fsn_nfb(d) >> 1;
+    for (unsigned j = blockIdx.x * 256u + threadIdx.x; j < n8; j += gridDim.x * 256u) {
+      const unsigned c = j % CH, r = j / CH;
+      const unsigned f = r % (unsigned)d.F, tb = r / (unsigned)d.F, b = tb % (unsigned)d.B;
+      const float den = mu[b] + 1e-5f;
+      const float* mrow = mt + (int64_t)tb * d.F;
+      const float* frow = fbo + (int64_t)tb * d.FP;
+      uint32_t pk[4];
+#pragma unroll
+      for (int e = 0; e < 8; e += 2) {
+        float x[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int k = (int)(8 * c) + e + u;
+          x[u] = k < d.NB ? mrow[reflect_idx((int)f - nn + k, d.F)] : k < W ? frow[reflect_idx((int)f - nf + (k - d.NB), d.F)] : 0.f;
+        }
+        pk[e >> 1] = (uint32_t)f2bf(x[0] / den) | ((uint32_t)f2bf(x[1] / den) << 16);
+      }
+      *reinterpret_cast<uint4*>(out + ((int64_t)r * WP + 8 * c) * 2) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+    }
+    return;
+  }
+  if (d.mode == 0 && d.dt == DT_BF16 && W == WP && (int64_t)d.TP * d.B * d.F * (W / 8) < (1LL << 31)) {
     // the default norm in bf16 plans (round 6): a thread forms 8 consecutive features of a row and stores them as ONE 16-byte chunk, its index split with
     // 32-bit divisions once per chunk (one thread per element: four 64-bit divisions and a 2-byte store each - 250 us for 203 MB at B = 64; same values)
     const unsigned CH = (unsigned)W / 8, n8 = (unsigned)d.TP * d.B * d.F * CH;
@@ -238,9 +264,10 @@ __global__ __launch_bounds__(256) void fsn_sbbuild_kernel(const Fsn d, const Are
     }
     return;
   }
-  GSL(i, (int64_t)d.TP * d.B * d.F * W) {
-    const int k = (int)(i % W);
-    const int64_t r = i / W;
+  GSL(i, (int64_t)d.TP * d.B * d.F * WP) {
+    const int k = (int)(i % WP);
+    const int64_t r = i / WP;
+    if (k >= W) { st_elem(out, d.dt, i, 0.f); continue; }
     const int f = (int)(r % d.F);
     const int64_t tb = r / d.F;
     const int b = (int)(tb % d.B), t = (int)(tb / d.B);
@@ -256,26 +283,53 @@ __global__ __launch_bounds__(256) void fsn_sbbuild_kernel(const Fsn d, const Are
     st_elem(out, d.dt, i, v);
   }
 }
-__global__ __launch_bounds__(256) void fsn_out_kernel(const Fsn d, const ArenaBases ab) {      // crm [B][F][T][2] <- sbo [TP][B*F][2]
+// output activation of a SequenceModel head (tools_for_model.py:766-775, 792-793) and its derivative at the pre-activation x; fp32
+__device__ __forceinline__ float head_act(int act, float x) {
+  return act == 1 ? fmaxf(x, 0.f) : act == 2 ? tanhf(x) : act == 3 ? fminf(fmaxf(x, 0.f), 6.f) : x;
+}
+__device__ __forceinline__ float head_act_grad(int act, float x, float g) {
+  if (act == 1) return x > 0.f ? g : 0.f;
+  if (act == 2) { const float y = tanhf(x); return g * (1.f - y * y); }
+  if (act == 3) return (x > 0.f && x < 6.f) ? g : 0.f;
+  return g;
+}
+__device__ __forceinline__ float head_act_grad_y(int act, float y, float g) {        // the same from the activation's OUTPUT y
+  if (act == 1) return y > 0.f ? g : 0.f;
+  if (act == 2) return g * (1.f - y * y);
+  if (act == 3) return (y > 0.f && y < 6.f) ? g : 0.f;
+  return g;
+}
+__global__ __launch_bounds__(256) void fsn_out_kernel(const Fsn d, const ArenaBases ab) {      // crm [B][F][T][2] <- act(sbo [TP][B*F][2])
   const float* sbo = reinterpret_cast<const float*>(rp(ab, d.in));
   float* crm = reinterpret_cast<float*>(rp(ab, d.out));
+  const int act = fsn_sbact(d);
   GSL(i, (int64_t)d.B * d.F * d.T * 2) {
     const int cch = (int)(i & 1);
     const int64_t q = i >> 1;
     const int t = (int)(q % d.T);
     const int64_t bf = q / d.T;
-    crm[i] = sbo[(((int64_t)(t + d.LA)) * d.B * d.F + bf) * 2 + cch];
+    const float v = sbo[(((int64_t)(t + d.LA)) * d.B * d.F + bf) * 2 + cch];
+    crm[i] = act ? head_act(act, v) : v;
   }
+}
+// in-place Tanh / ReLU6 on the full-band head's output [TP][B][FP] (act(0) = 0: the pad columns stay zero)
+__global__ __launch_bounds__(256) void fsn_act_kernel(const Fsn d, const ArenaBases ab) {
+  float* y = reinterpret_cast<float*>(rp(ab, d.out));
+  GSL(i, (int64_t)d.TP * d.B * d.FP) y[i] = head_act(d.act, y[i]);
 }
 __global__ __launch_bounds__(256) void fsn_out_bwd_kernel(const Fsn d, const ArenaBases ab) {  // d_sbo [TP][B*F][2] (dtype dt) <- grad_crm
   const float* g = reinterpret_cast<const float*>(rp(ab, d.in));
   char* ds = rp(ab, d.out);
+  const int act = fsn_sbact(d);
+  const float* pre = act ? reinterpret_cast<const float*>(rp(ab, d.aux)) : nullptr;     // sbo, the head's pre-activation: same [TP][B*F][2] layout
   GSL(i, (int64_t)d.TP * d.B * d.F * 2) {
     const int cch = (int)(i & 1);
     const int64_t q = i >> 1;
     const int64_t bf = q % ((int64_t)d.B * d.F);
     const int t = (int)(q / ((int64_t)d.B * d.F));
-    st_elem(ds, d.dt, i, t >= d.LA ? g[(bf * d.T + (t - d.LA)) * 2 + cch] : 0.f);
+    float v = t >= d.LA ? g[(bf * d.T + (t - d.LA)) * 2 + cch] : 0.f;
+    if (act && t >= d.LA) v = head_act_grad(act, pre[i], v);
+    st_elem(ds, d.dt, i, v);
   }
 }
 // S[b][f] = sum_{k,t} d_sbin * sbin   (in = d_sbin fp32 [TP][B*F][W], aux = sbin dtype dt)
@@ -283,11 +337,11 @@ __global__ __launch_bounds__(256) void fsn_sbbwd_sum_kernel(const Fsn d, const A
   const float* dsb = reinterpret_cast<const float*>(rp(ab, d.in));
   const char* sb = rp(ab, d.aux);
   float* sums = reinterpret_cast<float*>(rp(ab, d.sums));
-  const int f = blockIdx.x, b = blockIdx.y, W = d.NB + 1;
+  const int f = blockIdx.x, b = blockIdx.y, W = fsn_w(d), WP = fsn_wp(d);
   float s = 0.f;
   for (int i = threadIdx.x; i < d.TP * W; i += 256) {
     const int t = i / W, k = i % W;
-    const int64_t o = (((int64_t)t * d.B + b) * d.F + f) * W + k;
+    const int64_t o = (((int64_t)t * d.B + b) * d.F + f) * WP + k;
     s += dsb[o] * ld_elem(sb, d.dt, o);
   }
   __shared__ float red[4];
@@ -303,7 +357,7 @@ __global__ __launch_bounds__(256) void fsn_sbbwd_apply_kernel(const Fsn d, const
   const float* mu = reinterpret_cast<const float*>(rp(ab, d.aux2));
   const float* Sm = reinterpret_cast<const float*>(rp(ab, d.sums));     // S_b / N  (finalised as a "mean")
   char* out = rp(ab, d.out);
-  const int W = d.NB + 1;
+  const int W = fsn_wp(d);
   GSL(i, (int64_t)d.TP * d.B * d.FP) {
     const int f = (int)(i % d.FP);
     const int64_t tb = i / d.FP;
@@ -322,6 +376,54 @@ __global__ __launch_bounds__(256) void fsn_sbbwd_apply_kernel(const Fsn d, const
       else if (d.act == 3) v = (y > 0.f && y < 6.f) ? v : 0.f;   // ReLU6
     }
     st_elem(out, d.dt, i, v);
+  }
+}
+// fb_num_neighbors > 0: the transpose of the reflect gather.  Column NB + j of sub-band row f holds fb_out[reflect(f - nf + j)], so the gradient of
+// full-band bin g is the sum over the (f, j) with reflect(f - nf + j) == g: per j the regular source f = g + nf - j and, near the two edges, the
+// mirrored ones (p = -g, p = 2 (F - 1) - g).  One workgroup per (t, b): the NFB gradient columns of its F rows go to LDS with consecutive lanes
+// on consecutive addresses (runs of NFB floats; mode 0 reads them out of d_sb_in at stride WP, modes 1-3 from FSN_NORMBWD's dense [F][NFB]), then
+// one thread per bin adds its sources in a fixed order (j ascending; regular, low mirror, high mirror): no atomics, bit-reproducible.
+// mode 0 also applies the mean's term, once per source: d_fb[g] = (sum - cnt S_b / N) / (mu + eps).
+__global__ __launch_bounds__(256) void fsn_sbbwd_gather_kernel(const Fsn d, const ArenaBases ab) {
+  extern __shared__ float col[];                                          // [F][NFB]
+  const float* src = reinterpret_cast<const float*>(rp(ab, d.in));
+  const float* fbo = reinterpret_cast<const float*>(rp(ab, d.aux));
+  char* out = rp(ab, d.out);
+  const int NFB = fsn_nfb(d), nf = NFB >> 1, F = d.F;
+  const int ld = d.mode == 0 ? fsn_wp(d) : NFB, c0 = d.mode == 0 ? d.NB : 0;
+  const int64_t tb = blockIdx.x;
+  const int b = (int)(tb % d.B);
+  const float* rows = src + tb * F * ld + c0;
+  for (int i = threadIdx.x; i < F * NFB; i += 256) {
+    const int f = i / NFB, j = i - f * NFB;
+    col[i] = rows[(int64_t)f * ld + j];
+  }
+  __syncthreads();
+  for (int g = threadIdx.x; g < d.FP; g += 256) {
+    float v = 0.f;
+    if (g < F) {
+      float s = 0.f;
+      int cnt = 0;
+      for (int j = 0; j < NFB; ++j) {
+        const int o = nf - j;                                             // source row f = p + o for the un-reflected position p
+        int f = g + o;
+        if (f >= 0 && f < F) { s += col[f * NFB + j]; ++cnt; }
+        f = o - g;
+        if (g > 0 && f >= 0) { s += col[f * NFB + j]; ++cnt; }
+        f = 2 * (F - 1) - g + o;
+        if (g < F - 1 && f < F) { s += col[f * NFB + j]; ++cnt; }
+      }
+      if (d.mode == 0) {
+        const float* mu = reinterpret_cast<const float*>(rp(ab, d.aux2));
+        const float* Sm = reinterpret_cast<const float*>(rp(ab, d.sums));
+        const float den = mu[b] + 1e-5f;
+        v = s / den - (float)cnt * Sm[b] / den;
+      } else {
+        v = s;
+      }
+      v = head_act_grad_y(d.act, fbo[tb * d.FP + g], v);
+    }
+    st_elem(out, d.dt, tb * d.FP + g, v);
   }
 }
 
@@ -349,7 +451,7 @@ __global__ __launch_bounds__(256) void fsn_normstat_utt_kernel(const Fsn d, cons
   const float* fbo = d.src ? reinterpret_cast<const float*>(rp(ab, d.aux)) : nullptr;
   float* st = reinterpret_cast<float*>(rp(ab, d.stat));
   __shared__ double sh[4];
-  const int b = blockIdx.x, W = d.src ? d.NB + 1 : d.F, nf = d.src ? d.F : 1;
+  const int b = blockIdx.x, W = d.src ? fsn_w(d) : d.F, nf = d.src ? d.F : 1;
   const int64_t n = (int64_t)d.TP * nf * W;
   double s = 0, q = 0;
   for (int64_t i = threadIdx.x; i < n; i += 256) {
@@ -371,7 +473,7 @@ __global__ void fsn_normstat_cum_kernel(const Fsn d, const ArenaBases ab) {
   const float* fbo = d.src ? reinterpret_cast<const float*>(rp(ab, d.aux)) : nullptr;
   float* st = reinterpret_cast<float*>(rp(ab, d.stat));
   __shared__ double sh[4];
-  const int f = blockIdx.x, b = blockIdx.y, W = d.src ? d.NB + 1 : d.F;
+  const int f = blockIdx.x, b = blockIdx.y, W = d.src ? fsn_w(d) : d.F;
   const int64_t rows = d.src ? (int64_t)d.B * d.F : d.B, row = d.src ? (int64_t)b * d.F + f : b;
   double cs = 0, cq = 0;
   for (int t = 0; t < d.TP; ++t) {
@@ -396,30 +498,30 @@ __global__ __launch_bounds__(64) void fsn_normbwd_cum_kernel(const Fsn d, const 
   const float* fbo = reinterpret_cast<const float*>(rp(ab, d.aux));
   const float* st = reinterpret_cast<const float*>(rp(ab, d.stat));
   float* out = reinterpret_cast<float*>(rp(ab, d.out));
-  const int f = blockIdx.x, b = blockIdx.y, W = d.NB + 1, k = threadIdx.x;
+  const int f = blockIdx.x, b = blockIdx.y, W = fsn_w(d), WP = fsn_wp(d), NFB = fsn_nfb(d), k = threadIdx.x;
   const int64_t rows = (int64_t)d.B * d.F, row = (int64_t)b * d.F + f;
+  const int fsrc = reflect_idx(f - (NFB >> 1) + k, d.F);          // lane k < NFB owns full-band column k: out [TP][B][F][NFB]
   double accA = 0, accB = 0, accBM = 0;
   for (int t = d.TP - 1; t >= 0; --t) {
-    const int64_t o = ((int64_t)t * rows + row) * W;
+    const int64_t o = ((int64_t)t * rows + row) * WP;
     const float g = k < W ? dsb[o + k] : 0.f, y = k < W ? ld_elem(sb, d.dt, o + k) : 0.f;
     double G = g, S = (double)g * y;
+    if (k + 64 < W) { const float g2 = dsb[o + k + 64]; G += g2; S += (double)g2 * ld_elem(sb, d.dt, o + k + 64); }   // W <= 126
 #pragma unroll
     for (int sft = 32; sft > 0; sft >>= 1) { G += __shfl_xor(G, sft); S += __shfl_xor(S, sft); }
-    if (k == 0) {
-      const double m = st[((int64_t)t * rows + row) * 2], sd = st[((int64_t)t * rows + row) * 2 + 1], n = (double)W * (t + 1);
-      const double gk = dsb[o + d.NB];
-      double v;
-      if (d.mode == 1) {
-        const double den = m + (double)kNormEps;
-        accA += S / (den * n);
-        v = gk / den - accA;
-      } else {
-        const double bb = S / (n * sd * sd);
-        accA += G / (n * sd); accB += bb; accBM += bb * m;
-        v = gk / sd - accA - (double)fbo[((int64_t)t * d.B + b) * d.FP + f] * accB + accBM;
-      }
-      out[((int64_t)t * d.B + b) * d.F + f] = (float)v;
+    // G, S are the same in every lane after the butterfly: each lane keeps the row's suffix sums
+    const double m = st[((int64_t)t * rows + row) * 2], sd = st[((int64_t)t * rows + row) * 2 + 1], n = (double)W * (t + 1);
+    double v = 0;
+    if (d.mode == 1) {
+      const double den = m + (double)kNormEps;
+      accA += S / (den * n);
+      if (k < NFB) v = (double)dsb[o + d.NB + k] / den - accA;
+    } else {
+      const double bb = S / (n * sd * sd);
+      accA += G / (n * sd); accB += bb; accBM += bb * m;
+      if (k < NFB) v = (double)dsb[o + d.NB + k] / sd - accA - (double)fbo[((int64_t)t * d.B + b) * d.FP + fsrc] * accB + accBM;
     }
+    if (k < NFB) out[(((int64_t)t * d.B + b) * d.F + f) * NFB + k] = (float)v;
   }
 }
 // mode 2 (offline_gaussian_norm): dx = (g - G_b / N) / (sd_b + 1e-5) - y S_b / ((N - 1) sd_b);  sums[2][B][F] partial (S, G) per (b, f)
@@ -428,10 +530,10 @@ __global__ __launch_bounds__(256) void fsn_normbwd_utt_part_kernel(const Fsn d, 
   const char* sb = rp(ab, d.aux2);
   float* part = reinterpret_cast<float*>(rp(ab, d.sums));
   __shared__ double sh[4];
-  const int f = blockIdx.x, b = blockIdx.y, W = d.NB + 1;
+  const int f = blockIdx.x, b = blockIdx.y, W = fsn_w(d), WP = fsn_wp(d);
   double S = 0, G = 0;
   for (int i = threadIdx.x; i < d.TP * W; i += 256) {
-    const int64_t o = (((int64_t)(i / W) * d.B + b) * d.F + f) * W + i % W;
+    const int64_t o = (((int64_t)(i / W) * d.B + b) * d.F + f) * WP + i % W;
     const float g = dsb[o];
     G += g; S += (double)g * ld_elem(sb, d.dt, o);
   }
@@ -445,7 +547,7 @@ __global__ __launch_bounds__(256) void fsn_normbwd_utt_kernel(const Fsn d, const
   const float* st = reinterpret_cast<const float*>(rp(ab, d.stat));
   float* out = reinterpret_cast<float*>(rp(ab, d.out));
   __shared__ double tot[2];
-  const int b = blockIdx.y, W = d.NB + 1;
+  const int b = blockIdx.y, W = fsn_w(d), WP = fsn_wp(d), NFB = fsn_nfb(d);
   if (threadIdx.x < 2) {                                        // serial sum of F partials: deterministic, tiny
     double s = 0;
     for (int f = 0; f < d.F; ++f) s += part[(threadIdx.x * d.B + b) * d.F + f];
@@ -453,10 +555,11 @@ __global__ __launch_bounds__(256) void fsn_normbwd_utt_kernel(const Fsn d, const
   }
   __syncthreads();
   const double N = (double)d.F * W * d.TP, sdv = st[d.B + b], sden = sdv + 1e-5;
-  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < (int64_t)d.TP * d.F; i += (int64_t)gridDim.x * 256) {
-    const int f = (int)(i % d.F), t = (int)(i / d.F);
-    const int64_t o = (((int64_t)t * d.B + b) * d.F + f) * W + d.NB;
-    out[((int64_t)t * d.B + b) * d.F + f] = (float)((dsb[o] - tot[1] / N) / sden - (double)ld_elem(sb, d.dt, o) * tot[0] / ((N - 1) * sdv));
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < (int64_t)d.TP * d.F * NFB; i += (int64_t)gridDim.x * 256) {   // out [TP][B][F][NFB]
+    const int j = (int)(i % NFB);
+    const int f = (int)((i / NFB) % d.F), t = (int)(i / ((int64_t)NFB * d.F));
+    const int64_t o = (((int64_t)t * d.B + b) * d.F + f) * WP + d.NB + j;
+    out[(((int64_t)t * d.B + b) * d.F + f) * NFB + j] = (float)((dsb[o] - tot[1] / N) / sden - (double)ld_elem(sb, d.dt, o) * tot[0] / ((N - 1) * sdv));
   }
 }
 
@@ -497,16 +600,16 @@ void launch_fsn(const Op& op, const ArenaBases& ab, hipStream_t st) {
     case OP_FSN_SBSUM: {
       const Fsn& d = op.fsn;
       hipLaunchKernelGGL(fsn_sbsum_kernel, dim3(d.F, d.B), dim3(256), 0, st, d, ab);
-      hipLaunchKernelGGL(fsn_mean_kernel, dim3(d.B), dim3(64), 0, st, d, ab, (double)d.F * d.TP * (d.NB + 1), d.F);
+      hipLaunchKernelGGL(fsn_mean_kernel, dim3(d.B), dim3(64), 0, st, d, ab, (double)d.F * d.TP * fsn_w(d), d.F);
       break;
     }
-    case OP_FSN_SBBUILD: hipLaunchKernelGGL(fsn_sbbuild_kernel, dim3(gridn((int64_t)op.fsn.TP * op.fsn.B * op.fsn.F * (op.fsn.NB + 1))), dim3(256), 0, st, op.fsn, ab); break;
+    case OP_FSN_SBBUILD: hipLaunchKernelGGL(fsn_sbbuild_kernel, dim3(gridn((int64_t)op.fsn.TP * op.fsn.B * op.fsn.F * fsn_wp(op.fsn))), dim3(256), 0, st, op.fsn, ab); break;
     case OP_FSN_OUT: hipLaunchKernelGGL(fsn_out_kernel, dim3(gridn((int64_t)op.fsn.B * op.fsn.F * op.fsn.T * 2)), dim3(256), 0, st, op.fsn, ab); break;
     case OP_FSN_OUT_BWD: hipLaunchKernelGGL(fsn_out_bwd_kernel, dim3(gridn((int64_t)op.fsn.TP * op.fsn.B * op.fsn.F * 2)), dim3(256), 0, st, op.fsn, ab); break;
     case OP_FSN_SBBWD_SUM: {
       const Fsn& d = op.fsn;
       hipLaunchKernelGGL(fsn_sbbwd_sum_kernel, dim3(d.F, d.B), dim3(256), 0, st, d, ab);
-      hipLaunchKernelGGL(fsn_mean_kernel, dim3(d.B), dim3(64), 0, st, d, ab, (double)d.F * d.TP * (d.NB + 1), d.F);
+      hipLaunchKernelGGL(fsn_mean_kernel, dim3(d.B), dim3(64), 0, st, d, ab, (double)d.F * d.TP * fsn_w(d), d.F);
       break;
     }
     case OP_FSN_NORMSTAT: {
@@ -526,7 +629,11 @@ void launch_fsn(const Op& op, const ArenaBases& ab, hipStream_t st) {
       }
       break;
     }
-    case OP_FSN_SBBWD_APPLY: hipLaunchKernelGGL(fsn_sbbwd_apply_kernel, dim3(gridn((int64_t)op.fsn.TP * op.fsn.B * op.fsn.FP)), dim3(256), 0, st, op.fsn, ab); break;
+    case OP_FSN_SBBWD_APPLY:
+      if (fsn_nfb(op.fsn) > 1) hipLaunchKernelGGL(fsn_sbbwd_gather_kernel, dim3(op.fsn.TP * op.fsn.B), dim3(256), (size_t)op.fsn.F * fsn_nfb(op.fsn) * 4, st, op.fsn, ab);
+      else hipLaunchKernelGGL(fsn_sbbwd_apply_kernel, dim3(gridn((int64_t)op.fsn.TP * op.fsn.B * op.fsn.FP)), dim3(256), 0, st, op.fsn, ab);
+      break;
+    case OP_FSN_ACT: hipLaunchKernelGGL(fsn_act_kernel, dim3(gridn((int64_t)op.fsn.TP * op.fsn.B * op.fsn.FP)), dim3(256), 0, st, op.fsn, ab); break;
     default: break;
   }
 }

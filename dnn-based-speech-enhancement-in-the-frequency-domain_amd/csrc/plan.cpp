@@ -2347,7 +2347,7 @@ Plan* build_frontend_plan(const ModelConfig& cfg) {
 
 // =================================================================================================================
 // FullSubNet (reference models.py:568-682; SequenceModel tools_for_model.py:726-795).  model == 3.
-// Config fields reused: kernel_num = {sb_num_neighbors, fb_num_neighbors(=0), look_ahead, fb_hidden, sb_hidden,
+// Config fields reused: kernel_num = {sb_num_neighbors, fb_num_neighbors, look_ahead, fb_hidden, sb_hidden,
 //                                     fb activation (0 none, 1 ReLU, 2 Tanh, 3 ReLU6), sb activation, dropout keep in 1/1000};
 // T = frames of the input magnitude (passed in cfg.L as T, cfg.fft_len/2+1 = F).  I/O: io.mag [B][F][T] -> io.crm [B][F][T][2];
 // backward: io.grad_crm -> A_GRAD.
@@ -2368,12 +2368,17 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
   if (nmode < 0 || nmode > 3) { P->error = "FullSubNet: unknown norm_type"; return P; }
   const int NG = gru ? 3 : 4;                     // gate blocks of the recurrent weights
   const int adt = cfg.act_dtype;
-  const int TP = T + LA, NB = 2 * nsb + 1, W = NB + 1;
+  // sub-band rows: NB magnitude neighbours + NFB full-band neighbours = W features, stored WP = roundup(W, 8) wide (sefd_desc.h struct Fsn)
+  const int TP = T + LA, NB = 2 * nsb + 1, NFB = 2 * nfb + 1, W = NB + NFB, WP = (int)rup(W, 8);
   const int FP = (int)rup(F, 8);
   P->T = T;
   P->NF = F;
-  if (nfb != 0 || acts != 0) { P->error = "FullSubNet: fb_num_neighbors must be 0 and the sub-band output activation None"; return P; }
-  if (Hf % 8 || Hs % 8 || W % 8) { P->error = "FullSubNet: hidden sizes and sub-band width must be multiples of 8"; return P; }
+  if (nsb < 0 || nfb < 0 || nsb > kFsnMaxNeighbors || nfb > kFsnMaxNeighbors || F <= kFsnMaxNeighbors || (int64_t)F * NFB * 4 > 65536) {
+    P->error = "FullSubNet: sb_num_neighbors and fb_num_neighbors must lie in 0 .. " + std::to_string(kFsnMaxNeighbors) + " (and below num_freqs; num_freqs * (2 fb_num_neighbors + 1) <= 16384)";
+    return P;
+  }
+  if (actf < 0 || actf > 3 || acts < 0 || acts > 3) { P->error = "FullSubNet: unknown output activation"; return P; }
+  if (Hf % 8 || Hs % 8) { P->error = "FullSubNet: hidden sizes must be multiples of 8"; return P; }
   struct Net { std::string name; int I, H, O; };
   Net nets[2] = {{"fb_model", F, Hf, F}, {"sb_model", W, Hs, 2}};
   for (auto& nt : nets) {
@@ -2397,7 +2402,7 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
   std::vector<Op>& R = P->bwd;
 
   auto fsn0 = [&]() { Fsn f; std::memset(&f, 0, sizeof(f)); f.in = f.out = f.aux = f.aux2 = f.sums = f.stat = b.none();
-                      f.B = B; f.F = F; f.T = T; f.TP = TP; f.FP = FP; f.NB = NB; f.LA = LA; f.dt = adt; f.act = actf; return f; };
+                      f.B = B; f.F = F; f.T = T; f.TP = TP; f.FP = FP; f.NB = NB; f.LA = LA; f.dt = adt; f.act = actf; f.ext = fsn_ext(nfb, acts); return f; };
   // time-major GEMM over all steps: rows (t, r), source [TP][rows][feat]
   auto seq_gemm = [&](Ptr x, int xdt, int64_t rows, int feat, int off, int len, int N, int ydt) {
     RunGemm g = Builder::gemm0();
@@ -2596,17 +2601,17 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
   Ptr fbo = b.ws("fbo", (int64_t)TP * B * FP, DT_F32);
   { Op& m = b.push(Fw, OP_MEMSET, 102); m.ms.dst = fbo; m.ms.bytes = (int64_t)TP * B * FP * 4; }   // pad columns F..FP-1 stay 0
   FcRt fcf = fc_forward("fb_model", h1, B, Hf, F, fbo, FP, actf == 1 ? kRunRelu : 0, 102);
-  if (actf > 1) { P->error = "FullSubNet: only ReLU / None full-band activations are on the HIP path"; return P; }
+  if (actf > 1) { Fsn f = fsn0(); f.out = fbo; b.push(Fw, OP_FSN_ACT, 102).fsn = f; }     // Tanh / ReLU6 in place (ReLU: the GEMM's epilogue)
 
   // ---- sub-band input (models.py:647-665)
   const int64_t rs = (int64_t)B * F;
   Ptr sum_sb = b.ws("sum_sb", (int64_t)B * F, DT_F32);
   Ptr mu_sb = b.ws("mu_sb", B, DT_F32);
-  Ptr sb_in = b.ws("sb_in", (int64_t)TP * rs * W, adt);
+  Ptr sb_in = b.ws("sb_in", (int64_t)TP * rs * WP, adt);
   if (nmode == 0) { Fsn f = fsn0(); f.in = mag_t; f.aux = fbo; f.sums = sum_sb; f.aux2 = mu_sb; b.push(Fw, OP_FSN_SBSUM, 200).fsn = f; }
   else { Fsn f = fsn0(); f.in = mag_t; f.aux = fbo; f.stat = st_sb; f.mode = nmode; f.src = 1; b.push(Fw, OP_FSN_NORMSTAT, 200).fsn = f; }
   { Fsn f = fsn0(); f.in = mag_t; f.aux = fbo; f.sums = mu_sb; f.out = sb_in; f.mode = nmode; f.stat = st_sb; b.push(Fw, OP_FSN_SBBUILD, 201).fsn = f; }
-  Ptr h2 = lstm_forward("sb_model", 0, 2, sb_in, W, W, rs, Hs, 202);
+  Ptr h2 = lstm_forward("sb_model", 0, 2, sb_in, WP, WP, rs, Hs, 202);     // W_ih packed with zero rows for the pad features (as FP pads F above)
   Ptr h3 = lstm_forward("sb_model", 1, 3, h2, Hs, Hs, rs, Hs, 203);
   Ptr sbo = b.ws("sbo", (int64_t)TP * rs * 2, DT_F32);
   FcRt fcs = fc_forward("sb_model", h3, rs, Hs, 2, sbo, 2, 0, 204);
@@ -2775,7 +2780,7 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
     LayerRt &Lf0 = layers[0], &Lf1 = layers[1], &Ls0 = layers[2], &Ls1 = layers[3];
     // sub-band head
     Ptr d_sbo = b.ws("d_sbo", (int64_t)TP * rs * 2, adt);
-    { Fsn f = fsn0(); f.in = io_gcrm; f.out = d_sbo; b.push(R, OP_FSN_OUT_BWD, 205).fsn = f; }
+    { Fsn f = fsn0(); f.in = io_gcrm; f.out = d_sbo; if (acts) f.aux = sbo; b.push(R, OP_FSN_OUT_BWD, 205).fsn = f; }
     // sub-band head: 2 outputs.  With the row-block kernels the [T x rows x H] fp32 gradient of h (4 GB written by a K = 2 GEMM, read back
     // by the recurrence) is never materialised: the kernel computes dh = d_sbo[.., 0] W_fc[0] + d_sbo[.., 1] W_fc[1] as it needs it
     Ls1.headfuse = Ls1.rowsk && !(tune_str("LSTM_HEADFUSE") && atoi(tune_str("LSTM_HEADFUSE")) == 0);
@@ -2794,8 +2799,8 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
     wg_hold = 0;
     if (dh16) Ls0.dhdt = adt;
     Ptr dh2 = dropout_bwd(Ls0, dh2d, 202);
-    Ptr d_sbin = b.ws("d_sbin", (int64_t)TP * rs * W, DT_F32);
-    lstm_backward(Ls0, dh2, true, d_sbin, W, 0, W, DT_F32, 202);
+    Ptr d_sbin = b.ws("d_sbin", (int64_t)TP * rs * WP, DT_F32);
+    lstm_backward(Ls0, dh2, true, d_sbin, WP, 0, WP, DT_F32, 202);
     // through the normalised concat into the full-band output
     Ptr sumS = b.ws("sum_S", (int64_t)B * F, DT_F32);
     Ptr Sm = b.ws("Sm", B, DT_F32);
@@ -2804,7 +2809,7 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
       { Fsn f = fsn0(); f.in = d_sbin; f.aux = sb_in; f.sums = sumS; f.aux2 = Sm; b.push(R, OP_FSN_SBBWD_SUM, 201).fsn = f; }
       { Fsn f = fsn0(); f.in = d_sbin; f.aux = fbo; f.aux2 = mu_sb; f.sums = Sm; f.out = d_fb; b.push(R, OP_FSN_SBBWD_APPLY, 200).fsn = f; }
     } else {
-      Ptr dpre = b.ws("d_fb_pre", (int64_t)TP * B * F, DT_F32);
+      Ptr dpre = b.ws("d_fb_pre", (int64_t)TP * B * F * NFB, DT_F32);    // one value per full-band column; FSN_SBBWD_APPLY gathers them per bin
       Ptr part = b.ws("normbwd_part", (int64_t)2 * B * F, DT_F32);
       { Fsn f = fsn0(); f.in = d_sbin; f.aux = fbo; f.aux2 = sb_in; f.stat = st_sb; f.sums = part; f.out = dpre; f.mode = nmode; f.src = 1;
         b.push(R, OP_FSN_NORMBWD, 201).fsn = f; }

@@ -398,13 +398,31 @@ struct Dropout {
 //   (running mean over all values of the row up to and including frame t, sqrt(running variance + eps)).
 // FSN_SCALE / FSN_SBBUILD with mode > 0 normalise with `stat`;  FSN_NORMBWD: gradient of the normalised sub-band input w.r.t. the full-band
 //   output column (through the value and through the statistics) -> out fp32 [TP][B][F]; FSN_SBBWD_APPLY with mode > 0 takes that as `in`.
+// Knobs beyond the default live in `ext` (0 = the default: one full-band column, no sub-band activation): bits 0-7 = 2 * fb_num_neighbors
+// (NFB - 1: the full-band window has NFB = 2 nf + 1 reflect-indexed columns, sb_in[.., NB + j] = fb_out[reflect(f - nf + j)]), bits 8-9 = the
+// sub-band head's activation (FSN_OUT / FSN_OUT_BWD; 0 none, 1 ReLU, 2 Tanh, 3 ReLU6; FSN_OUT_BWD reads the pre-activation from `aux`).
+// A sub-band row has W = NB + NFB features and is STORED WP = roundup(W, 8) wide (sb_in: pad columns zero; d_sb_in: pad columns unused), so
+// that rows are whole 16-byte chunks in bf16 at any W.  With NFB > 1 FSN_NORMBWD writes one value per full-band column, out fp32
+// [TP][B][F][NFB], and FSN_SBBWD_APPLY sums, per full-band bin g, the columns (f, j) with reflect(f - nf + j) == g in a fixed order.
+// FSN_ACT: in-place Tanh / ReLU6 on the full-band head's output `out` (fp32 [TP][B][FP]; ReLU rides the GEMM epilogue, kRunRelu).
 struct Fsn {
   Ptr in, out, aux, aux2, sums;
   int32_t B, F, T, TP, FP, NB, LA, dt;
   int32_t act, mode;
   Ptr stat;
-  int32_t src, pad_;
+  int32_t src, ext;
 };
+constexpr int kFsnMaxNeighbors = 31;     // both neighbour counts: NFB <= 63 columns fit one wave, F * NFB floats fit 64 KB of LDS (F <= 260)
+static inline int32_t fsn_ext(int nfb_neighbors, int sb_act) { return (int32_t)((2 * nfb_neighbors) | (sb_act << 8)); }
+#ifdef __HIPCC__
+#define SEFD_HD __host__ __device__
+#else
+#define SEFD_HD
+#endif
+SEFD_HD static inline int fsn_nfb(const Fsn& d) { return (d.ext & 0xff) + 1; }
+SEFD_HD static inline int fsn_w(const Fsn& d) { return d.NB + fsn_nfb(d); }
+SEFD_HD static inline int fsn_wp(const Fsn& d) { return (fsn_w(d) + 7) & ~7; }
+SEFD_HD static inline int fsn_sbact(const Fsn& d) { return (d.ext >> 8) & 3; }
 
 enum OpKind : int32_t {
   OP_RUNGEMM = 1, OP_WGRAD, OP_PACK, OP_UNPACK, OP_BN_FINALIZE, OP_BN_APPLY, OP_BN_BWD_REDUCE, OP_BN_BWD_APPLY,
@@ -418,6 +436,7 @@ enum OpKind : int32_t {
   OP_ISTFT_FFT,
   OP_FSN_NORMSTAT, OP_FSN_NORMBWD,   // cfg.norm_type other than offline_laplace_norm (struct Fsn)
   OP_CBN_STATS, OP_CBN_FINALIZE, OP_CBN_APPLY, OP_CBN_BWD_REDUCE, OP_CBN_BWD_FINALIZE, OP_CBN_BWD_APPLY,   // ComplexBatchNorm (CbnFwd / CbnBwd)
+  OP_FSN_ACT,                        // Tanh / ReLU6 of FullSubNet's full-band head (struct Fsn)
 };
 
 constexpr int kOpHold = 2;     // Op::join of a lane-1 op
@@ -461,11 +480,6 @@ struct Op {
 };
 
 // ---- job order of the row-block recurrence launches that run as ticket-drawn jobs (lstm_rows.hip; checked on the CPU by tests/test_plan_hostsim.py)
-#ifdef __HIPCC__
-#define SEFD_HD __host__ __device__
-#else
-#define SEFD_HD
-#endif
 // ---- first encoder layer on the fp32 spectrum (kRunEnc0, enc0.hip): the descriptor form its two kernels execute - one fp32 source, two runs
 // (frame t - 1, frame t) of 10 floats at 4 floats per output bin
 SEFD_HD inline bool enc0_form(const RunGemm& d) {

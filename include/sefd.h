@@ -27,8 +27,8 @@ typedef struct sefd_model_config {
   int32_t B, L;           /* batch, samples per clip */
   int32_t win_len, hop, fft_len;
   int32_t n_layers;
-  int32_t kernel_num[12]; /* cfg.dccrn_kernel_num; FullSubNet (model 3): sb/fb neighbours, look_ahead, fb/sb hidden, fb/sb activation,
-                             dropout keep in 1/1000, [8] sequence model (0 LSTM, 1 GRU), [9] norm type (0 offline_laplace_norm,
+  int32_t kernel_num[12]; /* cfg.dccrn_kernel_num; FullSubNet (model 3): sb/fb neighbours (each 0 .. 31), look_ahead, fb/sb hidden,
+                             fb/sb output activation (0 None, 1 ReLU, 2 Tanh, 3 ReLU6), dropout keep in 1/1000, [8] sequence model (0 LSTM, 1 GRU), [9] norm type (0 offline_laplace_norm,
                              1 cumulative_laplace_norm, 2 offline_gaussian_norm, 3 cumulative_layer_norm) */
   int32_t rnn_layers, rnn_units;
   int32_t mask_mode;      /* 0 'E', 1 'C', 2 'R' (cfg.masking_mode) */
