@@ -1,0 +1,136 @@
+// Front-end planners: the ConvSTFT front end on its own, torch.stft and torch.istft.
+#include "plan_builder.h"
+
+namespace sefd {
+
+// Front end only (model 2): ConvSTFT 'complex' of io.wav in the reference layout -> io.out_real / io.out_imag [B][NF][T].
+// Used by DCCRN.loss for the clean spectrum of the LMS loss (models.py:306-309).
+Plan* build_frontend_plan(const ModelConfig& cfg) {
+  Plan* P = new Plan();
+  P->cfg = cfg;
+  Builder b;
+  b.P = P;
+  b.c = cfg;
+  b.fe = Stft(cfg);
+  const int B = cfg.B, T = b.fe.T, NF = b.fe.NF;
+  P->T = T;
+  P->NF = NF;
+  Ptr io_wav = b.io("wav", (int64_t)B * cfg.L);
+  Ptr io_or = b.io("out_real", (int64_t)B * NF * T);
+  Ptr io_oi = b.io("out_imag", (int64_t)B * NF * T);
+  Ptr spec = b.ws("spec", (int64_t)B * T * b.fe.SW, DT_F32);
+  b.stft_fwd(P->fwd, 1, io_wav, spec);
+  SpecOut so;
+  std::memset(&so, 0, sizeof(so));
+  so.est = spec; so.out_real = io_or; so.out_imag = io_oi; so.B = B; so.T = T; so.NF = NF;
+  b.push(P->fwd, OP_SPECOUT_FWD, 2).so = so;
+  finish_plan(b, P, 0, 0);
+  return P;
+}
+
+// =================================================================================================================
+// torch.stft front end of FullSubNet (model 4; tools_for_model.py:628-648): centre / reflect padding, hop = cfg.hop,
+// periodic Hann(win_len) zero-padded to fft_len in the middle.  io.wav [B][L] -> io.spec = complex64 image [B][NF][T][2].
+Plan* build_torchstft_plan(const ModelConfig& cfg) {
+  Plan* P = new Plan();
+  P->cfg = cfg;
+  Builder b;
+  b.P = P;
+  b.c = cfg;
+  const int B = cfg.B, L = cfg.L, W = cfg.win_len, hop = cfg.hop, NFFT = cfg.fft_len;
+  const int pad = NFFT / 2, Lp = L + 2 * pad;
+  const int T = 1 + L / hop;
+  const int NF = NFFT / 2 + 1, NS = NF + 1, SW = NS * 2;
+  P->T = T;
+  P->NF = NF;
+  if (hop % 4 != 0 || pad >= L) { P->error = "torch.stft plan: hop must be a multiple of 4 and the clip longer than fft_len/2"; return P; }
+  Ptr io_wav = b.io("wav", (int64_t)B * L);
+  Ptr io_spec = b.io("spec", (int64_t)B * NF * T * 2);
+  Ptr wpad = b.ws("wpad", (int64_t)B * Lp, DT_F32);
+  Ptr spec = b.ws("spec", (int64_t)B * T * SW, DT_F32);
+  { Op& op = b.push(P->fwd, OP_REFLECTPAD, 1); op.rpad.src = io_wav; op.rpad.dst = wpad; op.rpad.B = B; op.rpad.L = L; op.rpad.pad = pad; }
+  std::vector<double> win(NFFT, 0.0);
+  const int left = (NFFT - W) / 2;
+  for (int j = 0; j < W; ++j) win[left + j] = 0.5 - 0.5 * std::cos(2.0 * kPi * j / W);
+  RunGemm g = Builder::gemm0();
+  g.x[0] = wpad; g.xdt = DT_F32; g.ydt = DT_F32;
+  g.bstride[0] = Lp; g.rowlen[0] = Lp; g.fstride[0] = hop; g.Tin[0] = 1;
+  g.M = B * T; g.Tout = 1; g.Fo = T;
+  g.nseg = 1; g.seg[0] = Seg{0, 0, 0, NFFT, 0};
+  g.N = SW;
+  Builder::layout_segs(g);
+  {
+    std::vector<float> wt((size_t)g.Npad * g.ldw, 0.f);
+    for (int nn = 2; nn < g.N; ++nn)
+      for (int j = 0; j < NFFT; ++j) {
+        const double ang = 2.0 * kPi * (double)(((int64_t)(nn / 2 - 1) * j) % NFFT) / NFFT;
+        wt[(size_t)nn * g.ldw + j] = (float)(((nn & 1) == 0 ? std::cos(ang) : -std::sin(ang)) * win[j]);
+      }
+    g.w = b.cst(wt.data(), (int64_t)wt.size() * 4);
+  }
+  g.y = spec; g.y_bstride = (int64_t)T * SW; g.y_fstride = SW;
+  b.push(P->fwd, OP_RUNGEMM, 2).g = g;
+  SpecOut so;
+  std::memset(&so, 0, sizeof(so));
+  so.est = spec; so.out_real = io_spec; so.out_imag = b.none(); so.B = B; so.T = T; so.NF = NF; so.mode = 3;
+  b.push(P->fwd, OP_SPECOUT_FWD, 3).so = so;
+  finish_plan(b, P, 0, 0);
+  return P;
+}
+
+// =================================================================================================================
+// torch.istft(n_fft, hop, win_length, hann_window(win_length), center=True, length=L) - the inverse front end of FullSubNet's
+// validation path (tools_for_model.py:651-680, called at trainer.py:341-345).  IO: spec [B][NF][T][2] (memory image of the
+// complex [B, NF, T] tensor, or the reference's real-pair [B, NF, T, 2]) -> wav [B][L].  Same two kernels as the ConviSTFT path:
+// the inverse-FFT frame kernel (its rank-2 "correction" table set to the irfft's half weights of the DC and Nyquist bins:
+//   irfft(X)[j] = (S[j] - Re X[0] / 2 - (-1)^j Re X[N/2] / 2) / (N/2),  S[j] = Re sum_{k <= N/2} X[k] e^{2 pi i k j / N})
+// and the overlap-add kernel with the window-envelope normaliser, without the clamp.
+Plan* build_torchistft_plan(const ModelConfig& cfg) {
+  Plan* P = new Plan();
+  P->cfg = cfg;
+  Builder b;
+  b.P = P;
+  b.c = cfg;
+  const int B = cfg.B, L = cfg.L, W = cfg.win_len, hop = cfg.hop, NFFT = cfg.fft_len;
+  const int pad = NFFT / 2;
+  const int T = 1 + L / hop;
+  const int NF = NFFT / 2 + 1, NS = NF + 1, SW = NS * 2;
+  P->T = T;
+  P->NF = NF;
+  if (NFFT != 512 || W > NFFT || pad >= L || (T - 1) * hop + NFFT < pad + L) { P->error = "torch.istft plan: fft_len must be 512 and the frames must cover the clip"; return P; }
+  Ptr io_spec = b.io("spec", (int64_t)B * NF * T * 2);
+  Ptr io_wav = b.io("wav", (int64_t)B * L);
+  Ptr est = b.ws("est", (int64_t)B * T * SW, DT_F32);
+  Ptr frames = b.ws("frames", (int64_t)B * T * NFFT, DT_F32);
+  std::vector<double> win(NFFT, 0.0);
+  const int left = (NFFT - W) / 2;
+  for (int j = 0; j < W; ++j) win[left + j] = 0.5 - 0.5 * std::cos(2.0 * kPi * j / W);
+  { Op& op = b.push(P->fwd, OP_MEMSET, 1); op.ms.dst = est; op.ms.bytes = (int64_t)B * T * SW * 4; }       // slot 0 of every frame stays 0
+  SpecOut so;
+  std::memset(&so, 0, sizeof(so));
+  so.est = est; so.out_real = io_spec; so.out_imag = b.none(); so.B = B; so.T = T; so.NF = NF; so.mode = 3; so.accumulate = 0;
+  b.push(P->fwd, OP_SPECOUT_BWD, 2).so = so;
+  {
+    std::vector<float> tw(1024);
+    for (int k = 0; k < 512; ++k) { tw[2 * k] = (float)std::cos(2.0 * kPi * k / 512.0); tw[2 * k + 1] = (float)std::sin(2.0 * kPi * k / 512.0); }
+    std::vector<float> c(4 * 257, 0.f);                  // [even | odd][re | im][k]
+    c[(0 * 2 + 0) * 257 + 0] = 0.5f; c[(0 * 2 + 0) * 257 + 256] = 0.5f;
+    c[(1 * 2 + 0) * 257 + 0] = 0.5f; c[(1 * 2 + 0) * 257 + 256] = -0.5f;
+    Op& op = b.push(P->fwd, OP_ISTFT_FFT, 3);
+    op.ifft.est = est; op.ifft.frames = frames; op.ifft.tw = b.cst(tw.data(), 4096); op.ifft.win = b.win512(win);
+    op.ifft.corr = b.cst(c.data(), (int64_t)c.size() * 4); op.ifft.nframes = (int64_t)B * T; op.ifft.W = NFFT;
+  }
+  const int Lp = (T - 1) * hop + NFFT;
+  std::vector<float> env(Lp, 0.f);
+  for (int t = 0; t < T; ++t)
+    for (int j = 0; j < NFFT; ++j) env[t * hop + j] += (float)(win[j] * win[j]);
+  Ola ola;
+  std::memset(&ola, 0, sizeof(ola));
+  ola.frames = frames; ola.wav = io_wav; ola.coff = b.cst(env.data(), (int64_t)env.size() * 4); ola.dwav = ola.dpad = b.none();
+  ola.B = B; ola.T = T; ola.L = L; ola.win = NFFT; ola.hop = hop; ola.trim = pad; ola.noclamp = 1;
+  b.push(P->fwd, OP_OLA_FWD, 4).ola = ola;
+  finish_plan(b, P, 0, 0);
+  return P;
+}
+
+}  // namespace sefd

@@ -1302,7 +1302,7 @@ void launch_rungemm(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
 static void launch_wgrad_wide(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
   static const int stages = env_stages("WG256_STAGES", 2);   // 2, 3 and 4 stages measure the same (+-1 %): 2 x 32 KB leaves LDS to the other stream's kernels
   static const bool dual = !(tune_str("WG_DUAL") && atoi(tune_str("WG_DUAL")) == 0);
-  if (d.flags & kRunOnesMfma) {                     // the ones run is not a k tile (plan.cpp wgrad())
+  if (d.flags & kRunOnesMfma) {                     // the ones run is not a k tile (plan_builder.h wgrad())
     dim3 grid1(((d.Npad + 255) / 256) * ((d.ldw - 64 + 255) / 256) * d.nsplit);
     if (dual) hipLaunchKernelGGL((wgrad_bf16_dma_kernel<256, 4, 256, 512, true, true>), grid1, dim3(512), 0, st, d, ab);
     else hipLaunchKernelGGL((wgrad_bf16_dma_kernel<256, 2, 256, 512, false, true>), grid1, dim3(512), 0, st, d, ab);

@@ -19,7 +19,7 @@ CASES = [
     ("small_R_mse", (16, 32, 32, 64, 64, 64), 128, "R", "MSE"),
     ("small_E_sisdr", (16, 32, 32, 64, 64, 64), 128, "E", "SI-SDR"),
     ("default_E_sisnr", (32, 64, 128, 256, 256, 256), 256, "E", "SI-SNR"),
-    ("wide_C_sdr", (16, 32, 32, 64, 64, 64), 512, "C", "SDR"),        # rnn_units 512: per-time-step LSTM path (plan.cpp `stepped`)
+    ("wide_C_sdr", (16, 32, 32, 64, 64, 64), 512, "C", "SDR"),        # rnn_units 512: per-time-step LSTM path (plan_dccrn.cpp `stepped`)
     ("real_E_sisnr", (16, 32, 32, 64, 64, 64), 256, "E", "SI-SNR"),   # cfg.lstm == 'real': nn.LSTM(2 layers) + tranform
     ("large_C_sisnr", (64, 128, 256, 512, 512, 512), 512, "C", "SI-SNR"),   # BASELINE configs[4]: DCCRN-large (2x channels, rnn_units 512)
     ("noskip_E_sisnr", (16, 32, 32, 64, 64, 64), 128, "E", "SI-SNR"),       # cfg.skip_type = False (models.py:107-137, 222-223)

@@ -50,7 +50,7 @@ def test_hostsim_forward_backward_vs_oracle(mode, loss):
 
 def test_hostsim_wide_lstm_takes_the_per_step_path():
     """rnn_units = 512 (DCCRN-large, BASELINE configs[4]): W_hh no longer fits one CU's registers, the planner emits one
-    recurrent GEMM per parameter set + one cell launch per time step on the same buffers (plan.cpp `stepped`)."""
+    recurrent GEMM per parameter set + one cell launch per time step on the same buffers (plan_dccrn.cpp `stepped`)."""
     kw = dict(kernel_num=(16, 32, 32, 64, 64, 64), rnn_units=512)
     plan = Plan(1, 2000, masking_mode="C", **kw)
     kinds = [plan.op_info(PHASE_FWD, i)["kind"] for i in range(plan.num_ops(PHASE_FWD))]
@@ -234,7 +234,7 @@ def test_fsn_weight_gradients_ride_the_second_lane():
 
 
 def test_fsn_upper_subband_layer_has_one_weight_gradient_gemm():
-    """Round 6 (plan.cpp lstm_backward cat2, rungemm.hip kRunOnesMfma = 2048): at the reference sizes (H = 384, row-block kernels) the upper sub-band
+    """Round 6 (plan_fsn.cpp lstm_backward cat2, rungemm.hip kRunOnesMfma = 2048): at the reference sizes (H = 384, row-block kernels) the upper sub-band
     layer's W_ih and W_hh gradients are ONE GEMM over [h1_t | h2_{t-1} | ones] = 384 + 384 + 64 packed columns; under the 256 x 256 tile the ones run is
     not a k tile (the flag).  Knob FSN_WGCAT2=0: two GEMMs (K = 384 + ones, K = 384) as before.  The per-op GPU test (FullSubNet, T = 11) and the
     goldens check the numbers; this checks the planner's shapes."""

@@ -42,6 +42,13 @@ for dt in ("fp32", "bf16"):
         (f"crn_{dt}_direct", dict(B=2, L=4000, act_dtype=dt, masking_mode="Direct(None make)", **CRN), {}),
         (f"crn_{dt}_world2", dict(B=2, L=4000, act_dtype=dt, masking_mode="E", bn_world=2, **CRN), {}),
         (f"crn_{dt}_stft_gemm", dict(B=2, L=4000, act_dtype=dt, masking_mode="E", **CRN), {"STFT_GEMM": 1}),
+        (f"crn_{dt}_noskip", dict(B=2, L=4000, act_dtype=dt, masking_mode="E", skip_type=False, **CRN), {}),
+        (f"crn_{dt}_eval", dict(B=2, L=4000, act_dtype=dt, masking_mode="E", training=False, **CRN), {}),
+        # the recurrent block of lstm="real": per-frame cells (by knob, by size), the early gradient bucket, spectral mapping
+        (f"dccrn_{dt}_lstm_real_stepped", dict(B=2, L=4000, act_dtype=dt, lstm="real", **SMALL), {"LSTM_STEPPED": 1}),
+        (f"dccrn_{dt}_lstm_real_rnn512", dict(B=2, L=4000, act_dtype=dt, lstm="real", kernel_num=(16, 32, 32, 64, 64, 64), rnn_units=512), {}),
+        (f"dccrn_{dt}_lstm_real_buckets2", dict(B=2, L=4000, act_dtype=dt, lstm="real", grad_buckets=2, **SMALL), {}),
+        (f"dccrn_{dt}_lstm_real_direct", dict(B=2, L=4000, act_dtype=dt, lstm="real", masking_mode="Direct(None make)", **SMALL), {}),
     ]
 MATRIX += [
     ("frontend", dict(B=2, L=8000, model="STFT"), {}),
@@ -59,11 +66,16 @@ MATRIX += [
     ("arm_ENC0_DIRECT=0+SPECPAD_FUSE=0", dict(ARM), {"ENC0_DIRECT": 0, "SPECPAD_FUSE": 0}),
 ]
 for knob, val in (("STFT_GEMM", 1), ("ENC0_DIRECT", 0), ("ENC0_BNFUSE", 0), ("BN_FUSE", 2), ("PHASE_MERGE_MAXN", 0), ("WG_SWAP", 0),
-                  ("MASK_COLSUM", 0), ("LANE_ALL", 0), ("LSTM_STEPPED", 1), ("ENC_BIAS_ZERO", 0)):
+                  ("MASK_COLSUM", 0), ("LANE_ALL", 0), ("LSTM_STEPPED", 1), ("ENC_BIAS_ZERO", 0), ("GX_MERGE", 0), ("DX_MERGE", 0),
+                  ("LSTM_CHUNKS", 1)):
     MATRIX.append((f"arm_{knob}={val}", dict(ARM), {knob: val}))
+MATRIX.append(("arm_LSTM_STEPPED=1+GX_MERGE=0", dict(ARM), {"LSTM_STEPPED": 1, "GX_MERGE": 0}))
 BASES = {"bench_BN_FUSE=0": "bench_dccrn_bf16_C_b32_3s", "dccrn_fp32_ENC_BIAS_ZERO=0": "dccrn_fp32_arm_base",
-         "arm_ENC0_DIRECT=0+SPECPAD_FUSE=0": "arm_ENC0_DIRECT=0", "crn_fp32_stft_gemm": "crn_fp32_mask", "crn_bf16_stft_gemm": "crn_bf16_mask",
+         "arm_ENC0_DIRECT=0+SPECPAD_FUSE=0": "arm_ENC0_DIRECT=0", "arm_LSTM_STEPPED=1+GX_MERGE=0": "arm_LSTM_STEPPED=1",
          "frontend_stft_gemm": "frontend"}
+for dt in ("fp32", "bf16"):
+    BASES.update({f"crn_{dt}_{arm}": f"crn_{dt}_mask" for arm in ("stft_gemm", "noskip", "eval")})
+    BASES.update({f"dccrn_{dt}_lstm_real_{arm}": f"dccrn_{dt}_lstm_real" for arm in ("stepped", "rnn512", "buckets2", "direct")})
 
 
 def plan_bytes(kw, knobs):
