@@ -469,7 +469,7 @@ __global__ __launch_bounds__(512) void cgemm256_kernel(const RunGemm d, const Ar
 }
 
 #ifdef SEFD_TUNING
-int g_cgemm256_dbg = -1;       // tuning builds (-DSEFD_TUNING: tools/probes, A/B libraries) only: kernel variant; -1 = read SEFD_CG256_DBG once
+int g_cgemm256_dbg = -1;       // tuning builds (-DSEFD_TUNING: tools/probes, A/B libraries) only: kernel variant set by a probe; -1 = the knob CG256_DBG, read per launch
 #endif
 
 // The planner decides which GEMMs take this kernel: it marks them (and packs their weights) with kRunWTile32.
@@ -486,8 +486,7 @@ bool launch_cgemm256(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
   } while (0)
 #ifdef SEFD_TUNING
   // wrong-result / experimental arms exist in tuning builds only: the product library has no switch that changes what a launch computes
-  if (g_cgemm256_dbg < 0) g_cgemm256_dbg = tune_str("CG256_DBG") ? atoi(tune_str("CG256_DBG")) : 0;
-  switch (g_cgemm256_dbg) {
+  switch (g_cgemm256_dbg >= 0 ? g_cgemm256_dbg : (int)tune_int("CG256_DBG", 0)) {
     case 1: SEFD_CG256_LAUNCH(1); return true;
     case 2: SEFD_CG256_LAUNCH(2); return true;
     case 4: SEFD_CG256_LAUNCH(4); return true;

@@ -32,7 +32,7 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ uint16_t f2bf(float f) { return (uint16_t)pack_bf16x2(f, 0.f); }
 
 // Epilogue transpose of the 32x32 MFMA accumulator layout.  A lane holds ONE column (lane & 31) and, per group q, the 4 consecutive rows
-// 8q + 4 (lane >> 5) + 0..3: stored as they sit, a tile leaves as 2-byte pieces (round 4, SEFD_CG256_DBG=8: the staged epilogue of the wide
+// 8q + 4 (lane >> 5) + 0..3: stored as they sit, a tile leaves as 2-byte pieces (round 4, CG256_DBG=8: the staged epilogue of the wide
 // kernel with 128 ds_write_b16 per lane was 28-34 % of its run time).  A 4 x 4 transpose inside each quad of lanes on PACKED bf16 pairs - two
 // DPP row exchanges (lane ^ 1 with a byte permute, lane ^ 2 with selects), 11 VALU operations per 4 values - leaves lane (lane & 3) = p with
 // row 8q + 4 (lane >> 5) + p and the 4 consecutive columns (lane & 28) .. + 3: one 8-byte store.  Must run with all 64 lanes active.

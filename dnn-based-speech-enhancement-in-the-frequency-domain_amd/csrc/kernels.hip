@@ -996,8 +996,7 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize2_kernel(const BnBwdApply 
 }
 
 static bool fin_two_level(int nblk, int C, hipStream_t st, FinScratch* fs, dim3* grid) {
-  static const bool on = !(tune_str("BN_FIN2") && atoi(tune_str("BN_FIN2")) == 0);
-  if (!on || nblk < 64 || C > kFinMaxC) return false;
+  if (nblk < 64 || C > kFinMaxC) return false;
   *fs = fin_scratch(st);
   if (!fs->sums) return false;
   const int nch = std::min(kFinMaxChunks, (nblk + 31) / 32);

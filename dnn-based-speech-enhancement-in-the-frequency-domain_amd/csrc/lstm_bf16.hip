@@ -334,11 +334,10 @@ template <int HMAX>
 static void launch_t(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd) {
   dim3 grid((d.B + 15) / 16, d.G);
   dim3 block(64 * (d.H / 16));
-  // SEFD_LSTM_RPW = 4 / 16 forces a variant for both directions, SEFD_LSTM_RPW_BWD for the backward alone (read per launch: the per-op test
+  // LSTM_RPW = 4 / 16 forces a variant for both directions, LSTM_RPW_BWD for the backward alone (read per launch: the per-op test
   // runs both variants in one process)
-  const char* ev = tune_str("LSTM_RPW");
-  const char* evb = tune_str("LSTM_RPW_BWD");
-  const int rpw_env = !fwd && evb ? atoi(evb) : ev ? atoi(ev) : 0;
+  const int rpw_both = (int)tune_int("LSTM_RPW", 0);
+  const int rpw_env = fwd ? rpw_both : (int)tune_int("LSTM_RPW_BWD", rpw_both);
   const bool spread = rpw_env ? rpw_env == 4 : (int64_t)((d.B + 3) / 4) * d.G <= 1024;      // one cell per lane while the chip has CUs to spare
   if (fwd && spread) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<HMAX, 4>), dim3((d.B + 3) / 4, d.G), block, 2 * 16 * (d.H + 8) * sizeof(uint16_t), st, d, ab);
   else if (fwd) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<HMAX, 16>), grid, block, 2 * 16 * (d.H + 8) * sizeof(uint16_t), st, d, ab);

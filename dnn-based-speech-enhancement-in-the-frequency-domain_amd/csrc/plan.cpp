@@ -28,15 +28,16 @@ void finalize_rungemms(Builder& b, Plan* P) {
     }
   // Wide-tile kernel (cgemm256.hip) for the bf16 layers that carry the FLOPs: N a multiple of 256, LDS-DMA-able runs, enough rows.
   // Its weights are packed K-tile major (kRunWTile32): a property of the packed BUFFER, so it is chosen only when every GEMM
-  // that reads the buffer qualifies, and the PACK table of the matrix is permuted here, once.  SEFD_CG256=0: 128 x 128 kernel
+  // that reads the buffer qualifies, and the PACK table of the matrix is permuted here, once.  Knob CG256=0: 128 x 128 kernel
   // everywhere (A/B runs).
   {
-    const bool wide = !(tune_str("CG256") && atoi(tune_str("CG256")) == 0);
-    const int wide_minm = tune_str("CG256_MINM") ? atoi(tune_str("CG256_MINM")) : 4096;
+    const bool wide = tune_on("CG256");
+    const bool minm_set = tune_has("CG256_MINM");
+    const int wide_minm = (int)tune_int("CG256_MINM", 4096);
     // ... and enough 256 x 256 tiles to occupy the chip: the projection's input gradient (M = B*T = 15 456, N = 256: 61 tiles on 256 CUs) ran
     // 65 us on the wide kernel; as 242 workgroups of the 128-row kernel it fills the chip: 33 us.  Only up to K = 1024: DCCRN-large's few-tile
     // GEMMs have K = 2048 and lost 0.75 ms per step on the 128-row kernel.  (Tests that lower MINM run small cases on purpose.)
-    const int wide_mintiles = tune_str("CG256_MINTILES") ? atoi(tune_str("CG256_MINTILES")) : (tune_str("CG256_MINM") ? 0 : 100);
+    const int wide_mintiles = minm_set ? 0 : 100;          // 50 / 200 tiles measure the same (profiles/r04_tuning_notes.md)
     std::map<int64_t, bool> elig;                            // weight buffer offset -> every reader (either phase) qualifies
     std::vector<Op*> all;
     for (auto* ops : {&P->fwd, &P->bwd})
@@ -45,7 +46,7 @@ void finalize_rungemms(Builder& b, Plan* P) {
       if (op->kind != OP_RUNGEMM || op->g.w.arena != A_WS) continue;
       const RunGemm& g = op->g;
       const bool e = wide && (g.flags & kRunAligned) && g.xdt == DT_BF16 && g.Npad % 256 == 0 && g.ldw % 64 == 0 && g.M >= wide_minm && g.n2 == 0 &&
-                     ((((g.M + 255) / 256) * (int64_t)(g.Npad / 256) >= wide_mintiles && (g.ldw >= 256 || tune_str("CG256_MINM"))) || g.ldw > 1024);
+                     ((((g.M + 255) / 256) * (int64_t)(g.Npad / 256) >= wide_mintiles && (g.ldw >= 256 || minm_set)) || g.ldw > 1024);
       // (... and at least four 64-deep K tiles: the layer-1 LSTM input GEMMs of the chunked forward - M 7 744, N 1024, K 128, 124 tiles - are all prologue and
       //  epilogue on the persistent 256 x 256 tile: 32 us each against 18 us on the 128-row kernel, round 6; the tests that lower MINM run small cases on purpose)
       auto it = elig.find(g.w.off);
@@ -70,7 +71,7 @@ void finalize_rungemms(Builder& b, Plan* P) {
         for (Op* op : all) if (op->kind == OP_RUNGEMM && op->g.w.arena == A_WS && op->g.w.off == kv.first) op->g.flags |= kRunWTile32;
     }
   }
-  if (tune_str("DUMP_GEMMS")) {                          // planner debugging: every GEMM descriptor of the plan on stderr
+  if (tune_has("DUMP_GEMMS")) {                          // planner debugging: every GEMM descriptor of the plan on stderr
     int ph = 0;
     for (auto* ops : {&P->fwd, &P->bwd}) {
       int i = 0;
@@ -115,8 +116,8 @@ void finalize_rungemms(Builder& b, Plan* P) {
   // Training plans: both phases' packs ride the second stream during the forward phase (they read only parameters; the backward's 57 us
   // pass sat in the serial loss section, the forward's in front of the STFT).  The forward packs are issued first and joined by the first
   // op that reads a packed matrix; the backward packs are issued right after that op (one launch of both slowed the STFT / spectrum
-  // kernels next to it and delayed the first GEMM by 55 us).  SEFD_PACK_EARLY=0 keeps one launch per phase at its head.
-  if (!(tune_str("PACK_EARLY") && atoi(tune_str("PACK_EARLY")) == 0) && !P->fwd.empty() && !P->bwd.empty() &&
+  // kernels next to it and delayed the first GEMM by 55 us).  Knob PACK_EARLY=0 keeps one launch per phase at its head.
+  if (tune_on("PACK_EARLY") && !P->fwd.empty() && !P->bwd.empty() &&
       P->fwd[0].kind == OP_PACKMULTI && P->bwd[0].kind == OP_PACKMULTI) {
     P->fwd[0].lane = 2;
     size_t first = 0;

@@ -222,7 +222,7 @@ struct Builder {
   // (caller plans the framing GEMM instead) for other transform sizes.
   bool stft_fft(std::vector<Op>& ops, int tag, Ptr src, Ptr spec, int B, int L, int T, int hop, int off, int NFFT,
                 const std::vector<double>& win) {
-    if (NFFT != 512 || (int)win.size() > 512 || tune_str("STFT_GEMM")) return false;
+    if (NFFT != 512 || (int)win.size() > 512 || tune_has("STFT_GEMM")) return false;
     if (fft_tw.arena < 0) {
       std::vector<float> tw(1024);
       for (int k = 0; k < 512; ++k) { tw[2 * k] = (float)std::cos(2.0 * kPi * k / 512.0); tw[2 * k + 1] = (float)std::sin(2.0 * kPi * k / 512.0); }
@@ -236,8 +236,8 @@ struct Builder {
     op.fft.corr = none(); op.fft.scale = 1.f; op.fft.lp = none(); op.fft.pair = fft_pair();
     return true;
   }
-  // two frames per transform in the bf16 plans only (stft_fft.hip); SEFD_STFT_PAIR=0 / 1 forces one form (A/B runs)
-  int fft_pair() const { return tune_str("STFT_PAIR") ? atoi(tune_str("STFT_PAIR")) != 0 : c.act_dtype == DT_BF16; }
+  // two frames per transform in the bf16 plans only (stft_fft.hip); STFT_PAIR=0 / 1 forces one form (A/B runs)
+  int fft_pair() const { return tune_int("STFT_PAIR", c.act_dtype == DT_BF16) != 0; }
   Ptr fft_tw = Ptr{-1, 0, 0};
   Ptr fft_corr = Ptr{-1, 0, 0};
   // rank-2 correction of the closed-form pinv synthesis basis: cE/cO[part][k] = sum over even/odd j < W of the
@@ -266,7 +266,7 @@ struct Builder {
   }
   // iSTFT synthesis est -> frames as an inverse FFT (istft_fft_kernel); false: plan the synthesis GEMM instead
   bool istft_fft(std::vector<Op>& ops, int tag, Ptr est, Ptr frames, int64_t nframes, int NFFT, const std::vector<double>& win) {
-    if (NFFT != 512 || (int)win.size() > 512 || tune_str("STFT_GEMM")) return false;
+    if (NFFT != 512 || (int)win.size() > 512 || tune_has("STFT_GEMM")) return false;
     if (fft_tw.arena < 0) return false;                      // the STFT helper creates the twiddle table first
     Op& op = push(ops, OP_ISTFT_FFT, tag);
     op.ifft.est = est; op.ifft.frames = frames; op.ifft.tw = fft_tw; op.ifft.win = win512(win); op.ifft.corr = istft_corr((int)win.size());
@@ -275,7 +275,7 @@ struct Builder {
   }
   // its backward: d est = Kinv . (frames of the padded waveform gradient) = the analysis transform with the same correction
   bool istft_bwd_fft(std::vector<Op>& ops, int tag, Ptr dpad, Ptr dest, int B, int Lp, int T, int hop, int NFFT, const std::vector<double>& win) {
-    if (NFFT != 512 || (int)win.size() > 512 || tune_str("STFT_GEMM") || fft_tw.arena < 0) return false;
+    if (NFFT != 512 || (int)win.size() > 512 || tune_has("STFT_GEMM") || fft_tw.arena < 0) return false;
     Op& op = push(ops, OP_STFT_FFT, tag);
     op.fft.src = dpad; op.fft.spec = dest; op.fft.tw = fft_tw; op.fft.win = win512(win);
     op.fft.B = B; op.fft.L = Lp; op.fft.T = T; op.fft.hop = hop; op.fft.off = 0; op.fft.lp_dt = 0;
@@ -761,42 +761,40 @@ struct Builder {
     //  3-stage ring needs 48 / 36 KiB, so the same grids still fit in one wave with room for the other stream's kernels).
     const bool narrow = runs_aligned(g, true);       // thin layers: 32 / 16 wide n tiles (aligned bf16 kernel only)
     int tn = narrow ? wgrad_tn(g.xdt, g.N, g.Npad) : (g.xdt == DT_BF16 && g.Npad >= 128) ? 128 : kWgTN;
-    // the layers that carry the FLOPs: 256 x 256 tile of the 8-wave kernel.  SEFD_WG256=0 keeps the 128 x 128 tile; SEFD_WG256_MINM
+    // the layers that carry the FLOPs: 256 x 256 tile of the 8-wave kernel.  WG256=0 keeps the 128 x 128 tile; WG256_MINM
     // lowers the row threshold (tests run the wide kernel on small cases)
-    const bool wide_on = !(tune_str("WG256") && atoi(tune_str("WG256")) == 0);
-    const int64_t wide_minm = tune_str("WG256_MINM") ? atoll(tune_str("WG256_MINM")) : 32768;
+    const bool wide_on = tune_on("WG256");
+    const int64_t wide_minm = tune_int("WG256_MINM", 32768);
     int tk = kWgTK;
     if (narrow && wide_on && g.Npad % 256 == 0 && g.ldw >= 384 && g.M >= wide_minm) { tn = 256; tk = 256; g.flags |= kRunWgWide; }
     else if (narrow && wide_on && g.Npad == 128 && g.ldw >= 1024 && g.M >= wide_minm) { tn = 128; tk = 512; g.flags |= kRunWgWide; }
     // a bias ones run that would open a k tile of its own (the data columns fill whole 256-wide tiles): the kernel forms the bias with a constant ones
     // operand in the workgroups of k tile 0 instead (kRunOnesMfma, rungemm.hip); ONES_MFMA=0 keeps the run a DMA'd column
     if ((g.flags & kRunWgWide) && tn == 256 && bias && g.nseg >= 2 && g.seg[g.nseg - 1].src < 0 && g.seg[g.nseg - 1].koff == g.ldw - 64 &&
-        (g.ldw - 64) % 256 == 0 && !(tune_str("ONES_MFMA") && atoi(tune_str("ONES_MFMA")) == 0))
+        (g.ldw - 64) % 256 == 0 && tune_on("ONES_MFMA"))
       g.flags |= kRunOnesMfma;
     const int64_t ldk = (g.flags & kRunOnesMfma) ? g.ldw - 64 : g.ldw;    // columns the k tiles cover
     // wg_rounds > 1 (FullSubNet): that many dispatch rounds of shorter workgroups - the launch shares the chip with a recurrence whose
     // second round leaves 2/3 of the CUs idle, and a workgroup that needs the whole kernel's duration on its CU cannot use such a hole
-    // SEFD_WG_ROUNDS / SEFD_WGW_ROUNDS (tuning): rounds of every weight-gradient GEMM / of the wide-tile ones when the model did not set its own
-    const int env_rounds = (g.flags & kRunWgWide) && tune_str("WGW_ROUNDS") ? atoi(tune_str("WGW_ROUNDS")) : tune_str("WG_ROUNDS") ? atoi(tune_str("WG_ROUNDS")) : 1;
+    // (DCCRN in 2, 3, 4 rounds, all or only the wide-tile weight-gradient GEMMs: no gain, profiles/r05_tuning_notes.md - one round unless the model asks)
     // Wide-tile launches of SHORT workgroups (at most 10 tiles, fewer than 8192 rows per workgroup at 256 slots) fill 224 CUs, not 256: beside them the
     // main stream's 160 KB-LDS GEMMs need whole CUs, and 220 instead of 250 workgroups leave every XCD four - DCCRN default 10.60 -> 10.50 ms per step
     // (slots 160 / 192 / 208 / 216 / 224 / 232 / 240 / 248: 10.59 / 10.55 / 10.53 / 10.50 / 10.50 / 10.61 / 10.61 / 10.59, profiles/r05_tuning_notes.md);
-    // DCCRN-large's launches (20 / 40 tiles, or 5 tiles of 19 000-row workgroups) LOSE 0.3-0.7 ms that way and keep 256.  SEFD_WGW_SLOTS overrides.
+    // DCCRN-large's launches (20 / 40 tiles, or 5 tiles of 19 000-row workgroups) LOSE 0.3-0.7 ms that way and keep 256.
     const int tiles_w = std::max(1, (int)(rup(std::min(g.N, g.Npad), tn) / tn * rup(ldk, tk) / tk));
     const bool short_wg = wg_rounds <= 1 && tiles_w <= 10 && (int64_t)g.M * tiles_w < (int64_t)8192 * 256;
-    const int wide_slots = tune_str("WGW_SLOTS") ? atoi(tune_str("WGW_SLOTS")) : (short_wg ? 224 : 256);
-    const int nscale = tune_str("WGN_SCALE") ? atoi(tune_str("WGN_SCALE")) : 100;      // tuning: percent of the slots of the narrow-tile launches
+    const int wide_slots = short_wg ? 224 : 256;
     // the first encoder layer's kernel on the spectrum (enc0.hip; 21 KB of LDS and <= 124 registers: up to 4 workgroups per CU).  Row splits
     // 512 / 768 / 1024 / 2048: 10.267 / 10.282 / 10.285 / 10.315 ms per step (three alternating runs each): the launch is not grid-bound, fewer partials fold faster
-    const int enc0_slots = tune_str("ENC0_WG_SLOTS") ? atoi(tune_str("ENC0_WG_SLOTS")) : 512;
-    const int slots = ((g.flags & kRunEnc0) ? enc0_slots : g.xdt == DT_BF16 ? ((g.flags & kRunWgWide) ? wide_slots : (tn == 128 ? 512 : tn == 64 ? 768 : 1024) * nscale / 100) : 768) * std::max(1, wg_rounds > 1 ? wg_rounds : env_rounds);
+    const int enc0_slots = (int)tune_int("ENC0_WG_SLOTS", 512);
+    const int slots = ((g.flags & kRunEnc0) ? enc0_slots : g.xdt == DT_BF16 ? ((g.flags & kRunWgWide) ? wide_slots : (tn == 128 ? 512 : tn == 64 ? 768 : 1024)) : 768) * std::max(1, wg_rounds);
     const int tiles = (int)(rup(std::min(g.N, g.Npad), tn) / tn * rup(ldk, tk) / tk);   // tiles that hold real rows
     const int steps = (int)((g.M + kWgRows - 1) / kWgRows);
     int ns = std::max(1, slots / tiles);
     ns = std::max(1, std::min(ns, std::max(1, steps / 4)));
-    // N <= 4 outputs over a contiguous array (FullSubNet's sub-band head): the streaming kernel, one workgroup per row split (WGRANK=0: the tiled kernels;
-    // WGRANK_MINM: fewest rows, tests lower it)
-    if (wgrad_rank_form(g) && g.M >= (tune_str("WGRANK_MINM") ? atoll(tune_str("WGRANK_MINM")) : 65536) && !(tune_str("WGRANK") && atoi(tune_str("WGRANK")) == 0)) {
+    // N <= 4 outputs over a contiguous array (FullSubNet's sub-band head): the streaming kernel, one workgroup per row split, 0.48 ms per step ahead of the tiled
+    // kernels (profiles/r06_tuning_notes.md); WGRANK_MINM: fewest rows, tests lower it
+    if (wgrad_rank_form(g) && g.M >= tune_int("WGRANK_MINM", 65536)) {
       g.flags |= kRunRank;
       ns = std::max(1, std::min(1024, steps / 4));
     }
@@ -832,12 +830,11 @@ struct Builder {
 
   // Split sums: nothing reads a weight gradient's partial sums before the UNPACK that gathers them, so the folds of ALL weight gradients
   // planned since the last UNPACK wait in `pending_sums` and become ONE table-driven SPLITSUM launch in front of it (43 launches of
-  // 6-20 us on the weight-gradient lane before: 0.37 ms per step).  SEFD_SPLITSUM_MULTI=0 plans one SPLITSUM behind every WGRAD again.
+  // 6-20 us on the weight-gradient lane before: 0.37 ms per step).  SPLITSUM_MULTI=0 plans one SPLITSUM behind every WGRAD again.
   struct SumSeg { int64_t rel, n, ns; };
   std::vector<SumSeg> pending_sums;
   void split_sum(std::vector<Op>& ops, int64_t rel, int64_t n, int64_t ns, int tag) {
-    const bool multi = !(tune_str("SPLITSUM_MULTI") && atoi(tune_str("SPLITSUM_MULTI")) == 0);
-    if (multi) { pending_sums.push_back(SumSeg{rel, n, ns}); return; }
+    if (tune_on("SPLITSUM_MULTI")) { pending_sums.push_back(SumSeg{rel, n, ns}); return; }
     Op& os = push(ops, OP_SPLITSUM, tag);
     os.unpack.n = n;
     os.unpack.sstride = n;

@@ -33,10 +33,10 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
   // bf16 mode runs the cluster kernels of lstm_cluster.hip (W_hh spread over H/64 CUs, h handed over in memory every step);
   // fp32 mode and odd sizes fall back to one GEMM + one cell launch per time step on the same buffers.
   const bool cluster_ok = adt == DT_BF16 && H > 128 && H <= 512 && H % 64 == 0;
-  const bool stepped = (H > 128 && !cluster_ok) || tune_str("LSTM_STEPPED") != nullptr;
+  const bool stepped = (H > 128 && !cluster_ok) || tune_has("LSTM_STEPPED");
   // all weight gradients ride the second stream (after the fork they run next to the encoder's dgrad / BatchNorm chain and
-  // fill the tails of its kernels: 14.42 -> 14.30 ms/step); SEFD_LANE_ALL=0 keeps only the decoder's there
-  const bool lane_all = !(tune_str("LANE_ALL") != nullptr && atoi(tune_str("LANE_ALL")) == 0);
+  // fill the tails of its kernels: 14.42 -> 14.30 ms/step); LANE_ALL=0 keeps only the decoder's there
+  const bool lane_all = tune_on("LANE_ALL");
   if (H % 16 != 0 || (adt == DT_BF16 && H % 32 != 0)) { P->error = "rnn_units/2 must be a multiple of 16 (32 for bf16)"; return P; }
   if (Fe[n] < 1 || (Fe[0] % (1 << n)) != 0) { P->error = "fft_len/2 must be divisible by 2^n_layers"; return P; }
 
@@ -153,10 +153,10 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
   // bf16 plans (round 6): the first layer reads the fp32 spectrum itself - no padded copy (64 MB written and read per step at B = 32), K = 20 instead of
   // 128 mostly-zero columns; kernels: enc0.hip.  ENC0_DIRECT=0: the padded copy and the generic kernels (A/B runs)
   const bool enc0_direct = adt == DT_BF16 && spec_fft && NS == 258 && KS == 5 && Fe[1] == 128 && (ch[1] == 16 || ch[1] == 32 || ch[1] == 64) &&
-                           !(tune_str("ENC0_DIRECT") && atoi(tune_str("ENC0_DIRECT")) == 0);
+                           tune_on("ENC0_DIRECT");
   if (!enc0_direct) {
     spec_lp = b.ws("xin", (int64_t)B * T * NS * CP, adt);
-    const bool fuse_pad = !(tune_str("SPECPAD_FUSE") && atoi(tune_str("SPECPAD_FUSE")) == 0);
+    const bool fuse_pad = tune_on("SPECPAD_FUSE");
     if (spec_fft && fuse_pad && NS == 258) {      // the FFT kernel writes the padded copy beside the spectrogram (no SPECPAD pass: 48 us at B = 32)
       F.back().fft.lp = spec_lp; F.back().fft.lp_dt = adt;
     } else {
@@ -242,9 +242,9 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
   };
   // Two complex layers, persistent bf16 kernels: the sequence is cut into chunks of frames and layer 1 (combine + input
   // GEMM + recurrence of a chunk, second HIP stream) runs while layer 0 already works on the next chunk - the two 483-step
-  // recurrences (8 workgroups each, latency-bound) overlap instead of running back to back.  SEFD_LSTM_CHUNKS=1 disables.
+  // recurrences (8 workgroups each, latency-bound) overlap instead of running back to back.  LSTM_CHUNKS=1 disables.
   // Measured (B = 32, T = 483): 1 chunk 14.08 ms/step, 2-6 chunks 13.84-13.94, 8: 13.94, 16: 14.50 -> 4.
-  int nchunk = tune_str("LSTM_CHUNKS") ? atoi(tune_str("LSTM_CHUNKS")) : 4;
+  int nchunk = (int)tune_int("LSTM_CHUNKS", 4);
   if (!(cx && !stepped && adt == DT_BF16 && NL == 2) || nchunk < 2 || T < 8 * nchunk) nchunk = 1;
   const bool pipe = nchunk > 1;
   LstmRec pipe_rec[2];
@@ -267,7 +267,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       o[0] = pe(*bih[set], gq, 1); o[1] = pe(*bhh[set], gq, 1);
     };
     ls[l].bgx = bias;
-    const bool gx_merge = !(tune_str("GX_MERGE") && atoi(tune_str("GX_MERGE")) == 0) && BT * 8 * H < (1LL << 31);
+    const bool gx_merge = tune_on("GX_MERGE") && BT * 8 * H < (1LL << 31);
     for (int p = 0; p < 2; ++p) {
       RunGemm g = b.rows_gemm(lin, adt, rowlen, p * H, H, 8 * H, DT_F32);
       if (l == 0) Builder::rows_slices(g, D, Cl, p * (Cl / 2), Cl / 2);
@@ -340,8 +340,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       }
       // lane 3 (third stream): the input GEMM of layer 1 for this chunk reads layer 0's chunk only, so it runs BESIDE layer 1's recurrence
       // over the previous chunk instead of queueing behind it on the second stream (round 4 timeline: 657 -> ~520 us for the LSTM block)
-      static const bool lane3 = !(tune_str("LSTM_LANE3") && atoi(tune_str("LSTM_LANE3")) == 0);
-      b.cur_lane = lane3 ? 3 : 2;
+      b.cur_lane = 3;
       {
         Op& op = b.push(F, OP_COMBINE_FWD, 200);
         op.comb.h = ls[0].h; op.comb.out = ls[0].hc; op.comb.rows = BT; op.comb.H = H; op.comb.dt = adt;
@@ -433,13 +432,13 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
     const int npad_stat = (int)rup(Co, bn_of(Co));
     Ptr part = last ? b.none() : b.ws(nm + ".stat", (int64_t)2 * nblk1 * 2 * npad_stat, DT_F32);
     const bool stats = !last && cfg.training && !cbn;
-    // Thin layers (Cob <= SEFD_PHASE_MERGE_MAXN, default 32: dec4 and the mask layer): ONE GEMM for both sub-pixel phases - the even
+    // Thin layers (Cob <= PHASE_MERGE_MAXN, default 32: dec4 and the mask layer): ONE GEMM for both sub-pixel phases - the even
     // phase's runs (input bins f-1, f, f+1, two frames), 2 * Cob output columns [phase][channel] (= bins 2f and 2f+1 of the output row:
     // contiguous in the channels-last buffer), zero weights where the odd phase has no tap.  These layers are bound by streaming the
     // tap-expanded activation operand through L2 -> LDS, not by MFMAs: 20 % more MACs, the operand streamed once instead of twice.
     // The backward reads only the per-phase coefficient functions.
-    const int merge_maxn = tune_str("PHASE_MERGE_MAXN") ? atoi(tune_str("PHASE_MERGE_MAXN")) : 64;
-    const bool merge = Cob <= merge_maxn && !(tune_str("WG_SWAP") && atoi(tune_str("WG_SWAP")) == 0);
+    const int merge_maxn = (int)tune_int("PHASE_MERGE_MAXN", 64);
+    const bool merge = Cob <= merge_maxn && tune_on("WG_SWAP");
     src[1] = Builder::ActSrc{enc[idx - 1].z, (int64_t)T * Fi * C1, Fi * C1, 0, C1};
     dec_src[d] = src;
     b.dec_phases(F, 400 + d, nm, Ly, src, Fi, Cob, wcoef, stats ? part : b.none(), nblk1, !merge);
@@ -505,8 +504,8 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
     }
     b.conv_grads(enc, dec, std::max(ch[0], CP));
     constexpr int kCsRows = 2048;                // workgroups of MASK_BWD when it also leaves the mask layer's bias-gradient shares
-    const bool mask_colsum = !(tune_str("MASK_COLSUM") && atoi(tune_str("MASK_COLSUM")) == 0) && CP >= 2 && CP <= 8 &&
-                             !(tune_str("WG_SWAP") && atoi(tune_str("WG_SWAP")) == 0);
+    const bool mask_colsum = tune_on("MASK_COLSUM") && CP >= 2 && CP <= 8 &&
+                             tune_on("WG_SWAP");
     int mask_colsum_op = -1;
     Ptr d_decin = b.ws("decin.d", BT * D * Cl, adt);
     {
@@ -523,8 +522,8 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
     // (cgemm256, N % 256 == 0, compute-bound) 10-17 us per launch against 38-91 us for the pass it replaces, but it costs the thin
     // GEMMs (N <= 128: latency-bound tiles that stream at ~2 TB/s) 45-85 us per launch - more than the pass, which streams at 4-5 TB/s.
     // So by default only the layers whose producers all run on the wide-tile kernel are fused (bf16, C % 256 == 0).
-    // SEFD_BN_FUSE=0: none; SEFD_BN_FUSE=2: every layer (the per-op tests run the epilogue of all three GEMM kernels that way).
-    const int bn_fuse_mode = tune_str("BN_FUSE") ? atoi(tune_str("BN_FUSE")) : 1;
+    // BN_FUSE=0: none; BN_FUSE=2: every layer (the per-op tests run the epilogue of all three GEMM kernels that way).
+    const int bn_fuse_mode = (int)tune_int("BN_FUSE", 1);
     const bool bn_fuse = bn_fuse_mode != 0 && !cbn;
     auto bn_fuse_layer = [&](int C, int64_t Rr) { return bn_fuse_mode == 2 || (adt == DT_BF16 && C % 256 == 0 && Rr >= 8192); };
     using BnbAcc = Builder::BnbAcc;
@@ -563,7 +562,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       const std::string pp = "decoder." + std::to_string(d);
       if (!last)
         b.bn_bwd(R, 400 + d, dec[d].y, dec[d].dz, b.none(), dec[d].mi, pp, Co, dec[d].R, (int64_t)(T + 1) * Fo, Fo, dec[d].dy, nm, cbn, &bnb_dec[d], false);
-      // Weight gradients.  Forward form (SEFD_WG_SWAP=0): one WGRAD per sub-pixel phase, A = the forward runs (3 or 2 taps x C channels of
+      // Weight gradients.  Forward form (WG_SWAP=0): one WGRAD per sub-pixel phase, A = the forward runs (3 or 2 taps x C channels of
       // both sources, two frames: every input element is streamed through LDS ~5 times per phase pair), dense operand = dy.
       // Swapped form (default): the SAME tensor, contracted over INPUT pixels - dense operand = the source activation x_s (each element
       // read once), A = the runs of the input-gradient GEMM over dy (5 taps x Co channels, two frames): the tap expansion moves to the
@@ -571,7 +570,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       // The bias gradient needs its own pass over dy then (ones run only) - planned for the mask layer; a conv bias in front of
       // BatchNorm has an identically zero gradient (the sum over all rows of the BatchNorm input gradient vanishes), which the reference
       // computes as rounding noise and this plan leaves at exactly 0.
-      const bool wg_swap = !(tune_str("WG_SWAP") && atoi(tune_str("WG_SWAP")) == 0);
+      const bool wg_swap = tune_on("WG_SWAP");
       b.cur_lane = 1;                           // weight gradients of the decoder: nothing downstream needs them before UNPACK
       if (!wg_swap) for (int par = 0; par < 2; ++par) b.wgrad(R, dec[d].f[par], dec[d].dy, dec[d].coef[par], 400 + d, &dec[d].bias);
       else if (!last) {                          // conv biases in front of BatchNorm: UNPACK writes their exact zero
@@ -611,7 +610,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       // Thin layers: ONE GEMM over dy for the input gradients of both sources (previous layer's output | skip connection): the same runs
       // of dy, C0 + C1 output columns, the second half stored to the second destination (RunGemm::y2 / n2).  The A operand - what bounds
       // these layers - is streamed once instead of twice.  Not when a destination's BatchNorm sums ride in the epilogue (one layer per GEMM).
-      const int dg_maxn = tune_str("DGRAD_MERGE_MAXN") ? atoi(tune_str("DGRAD_MERGE_MAXN")) : 128;
+      const int dg_maxn = (int)tune_int("DGRAD_MERGE_MAXN", 128);
       const bool dg_merge = nsrc == 2 && C0 == C1 && C0 % 8 == 0 && C0 + C1 <= dg_maxn && !(d > 0 && bnb_dec[d - 1].on) && !bnb_enc[idx - 1].on;
       RunGemm dg_g[2];
       Builder::Coef dg_coef[2];
@@ -723,7 +722,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       // does not feed an output column is zero - writing the whole [D][Cl] row of d_encz contiguously, instead of 2 x D launches of
       // N = Cl / 2 (M = B*T rows only: 8 x 24 us of latency-bound tiles vs one wide-tile launch; twice the MACs, 65 GFLOP).
       const bool dx_merge = l == 0 && adt == DT_BF16 && (D * Cl) % 256 == 0 && (8 * H) % 64 == 0 &&
-                            !(tune_str("DX_MERGE") && atoi(tune_str("DX_MERGE")) == 0);
+                            tune_on("DX_MERGE");
       if (dx_merge) {
         RunGemm g = b.rows_gemm(dyp(0), adt, 8 * H, 0, 8 * H, D * Cl, adt);
         g.x[1] = dyp(1); g.bstride[1] = g.bstride[0]; g.tstride[1] = 8 * H; g.rowlen[1] = 8 * H; g.Tin[1] = T;     // part 1: a second source
@@ -758,13 +757,13 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
     // a caller can start their all-reduce while the encoder backward still runs (sefd_plan_grad_bucket / sefd_plan_run_cb).
     // The folds of the decoder + LSTM weight gradients (3/4 of the 1.2 GB of partial sums of a step) go here, on the weight-gradient lane:
     // a bandwidth-bound pass beside the encoder's input-gradient GEMMs instead of in front of the final UNPACK on the main stream.
-    if (!(tune_str("SPLITSUM_MID") && atoi(tune_str("SPLITSUM_MID")) == 0)) b.flush_sums(R, 997, true);
+    if (tune_on("SPLITSUM_MID")) b.flush_sums(R, 997, true);
     // Without an exchange (one bucket) the same early UNPACK rides the weight-gradient lane (tag 997): the gather of 83 % of the parameters
-    // leaves the tail of the main stream (79 us for all of them in front of Adam before); SEFD_UNPACK_MID=0 keeps the single UNPACK.
-    const bool unpack_mid = cfg.grad_buckets < 2 && !(tune_str("UNPACK_MID") && atoi(tune_str("UNPACK_MID")) == 0);
+    // leaves the tail of the main stream (79 us for all of them in front of Adam before); UNPACK_MID=0 keeps the single UNPACK.
+    const bool unpack_mid = cfg.grad_buckets < 2 && tune_on("UNPACK_MID");
     if (cfg.grad_buckets >= 2 || unpack_mid) {
       const int64_t lo = b.par("decoder.0.0.real_conv.weight").off;
-      b.flush_sums(R, 997, unpack_mid);                      // (nothing pending unless SEFD_SPLITSUM_MID=0)
+      b.flush_sums(R, 997, unpack_mid);                      // (nothing pending unless SPLITSUM_MID=0)
       if (unpack_mid) b.cur_lane = 1;
       b.unpack_range(R, lo, nparam, unpack_mid ? 997 : 998);
       b.cur_lane = 0;
@@ -780,17 +779,17 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       // BN_BWD_APPLY is not planned, the weight-gradient kernel takes dz through the BatchNorm + PReLU backward as it loads it (kRunDyFromBn) and runs on
       // the MAIN stream right behind BN_BWD_FINALIZE: apply (117 us) -> fold -> weight gradient (52 us) was the serial tail of the step.  ENC0_BNFUSE=0: off
       const bool dy_fused = i == 0 && (enc[0].f[0].flags & kRunEnc0) && enc0_accepts(enc[0].f[0], true) && !cbn &&    // (its weight gradient's form: sefd_desc.h)
-                            !(tune_str("ENC0_BNFUSE") && atoi(tune_str("ENC0_BNFUSE")) == 0);
+                            tune_on("ENC0_BNFUSE");
       const BnBwdApply bnb = b.bn_bwd(R, 100 + i, enc[i].y, enc[i].dz, cfg.skip ? enc[i].dskip : b.none(), enc[i].mi, pp, Co, enc[i].R, (int64_t)T * Fo, 0,
                                       enc[i].dy, nm, cbn, &bnb_enc[i], dy_fused);
       // the folds of enc5 .. enc1 go in front of the LAST weight gradient on its lane (its input is the last thing the dgrad chain produces,
       // the lane usually waits for it): the fold in front of the final UNPACK then covers one thin layer
-      if (i == 0 && lane_all && n > 1 && !(tune_str("SPLITSUM_MID") && atoi(tune_str("SPLITSUM_MID")) == 0)) b.flush_sums(R, 996, true);
+      if (i == 0 && lane_all && n > 1 && tune_on("SPLITSUM_MID")) b.flush_sums(R, 996, true);
       b.cur_lane = (lane_all && !dy_fused) ? 1 : 0;             // encoder weight gradients next to the dgrad chain
       // Every encoder conv bias sits in front of a training-mode BatchNorm: its gradient is identically zero (the sum over all rows of the
       // BatchNorm input gradient vanishes; the reference computes rounding noise there).  No bias "ones" run in these GEMMs - it cost a
       // whole 64-column K segment (enc0: 192 -> 128 columns, half the K tiles; enc3: 6 -> 5 wide tiles) - UNPACK writes the exact zero.
-      const bool enc_bias_zero = !(tune_str("ENC_BIAS_ZERO") && atoi(tune_str("ENC_BIAS_ZERO")) == 0);
+      const bool enc_bias_zero = tune_on("ENC_BIAS_ZERO");
       if (enc_bias_zero) {
         b.zero_grad.resize(nparam, 0);
         for (const char* part : {".0.real_conv.bias", ".0.imag_conv.bias"}) {
@@ -818,7 +817,7 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       // dx[ci,f,t] = sum W[co,ci,kh,kw] dy[co,(f+2-kh)/2, t+1-kw]  -> two sub-pixel phases over dy [B][T][Fo][Co]
       // thin layers: both phases in one GEMM over the even phase's runs (see the decoder forward), unless this layer's BatchNorm sums
       // ride in the epilogue (their partial rows have one column per channel)
-      const int merge_maxn = tune_str("PHASE_MERGE_MAXN") ? atoi(tune_str("PHASE_MERGE_MAXN")) : 64;
+      const int merge_maxn = (int)tune_int("PHASE_MERGE_MAXN", 64);
       if (Ci <= merge_maxn && !bnb_enc[i - 1].on) {
         RunGemm g = Builder::gemm0();
         g.x[0] = enc[i].dy; g.xdt = adt; g.ydt = adt;

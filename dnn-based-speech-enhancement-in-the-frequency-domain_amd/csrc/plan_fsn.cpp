@@ -110,11 +110,11 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
     L.Whh = &Whh;
     const int I = (int)Wih.shape[1];
     // thousands of rows (the sub-band model) in bf16: row-block kernels (lstm_rows.hip) on a packed bf16 copy of W_hh; their gate
-    // slabs are bf16 too - at B * 257 rows those layers are bound by the HBM traffic of exactly these slabs (SEFD_LSTM_SLAB32=1: fp32)
-    const int64_t rows_min = tune_str("LSTM_ROWS_MIN") ? atoll(tune_str("LSTM_ROWS_MIN")) : 1024;
-    L.cluster = !gru && adt == DT_BF16 && H > 128 && H <= 512 && H % 64 == 0 && tune_str("LSTM_STEPPED") == nullptr;
+    // slabs are bf16 too - at B * 257 rows those layers are bound by the HBM traffic of exactly these slabs (LSTM_SLAB32=1: fp32)
+    const int64_t rows_min = tune_int("LSTM_ROWS_MIN", 1024);
+    L.cluster = !gru && adt == DT_BF16 && H > 128 && H <= 512 && H % 64 == 0 && !tune_has("LSTM_STEPPED");
     L.rowsk = L.cluster && rows >= rows_min && (H == 256 || H == 384 || H == 512);
-    L.sdt = (L.rowsk && tune_str("LSTM_SLAB32") == nullptr) ? DT_BF16 : DT_F32;
+    L.sdt = (L.rowsk && !tune_has("LSTM_SLAB32")) ? DT_BF16 : DT_F32;
     L.gates = b.ws(L.nm + ".gates", (int64_t)TP * rows * 4 * H, L.sdt);
     L.c = b.ws(L.nm + ".c", (int64_t)TP * rows * H, DT_F32);
     L.h = b.ws(L.nm + ".h", (int64_t)TP * rows * H, adt);
@@ -128,10 +128,10 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
     b.pack_weights(Fw, g, L.cgx, L.nm + ".ih", tag, &L.bgx);
     set_y(g, L.gates, rows, 4 * H, 0);
     // row-block kernels, 32 input features (the sub-band model's first layer): the input projection is fused into the recurrence (one more
-    // k-step per frame) instead of writing and re-reading a [T x rows x 4H] pre-activation slab (8 GB at B = 64); SEFD_LSTM_XFUSE=0 keeps the GEMM
+    // k-step per frame) instead of writing and re-reading a [T x rows x 4H] pre-activation slab (8 GB at B = 64); LSTM_XFUSE=0 keeps the GEMM
     // ... and the layers above it (input = the layer below's h, H features): H/32 more k-steps per frame instead of an 8 GB slab + a GEMM
     const bool x32 = xlen == 32 && xfeat == 32 && g.ldw == 64, xh = xlen == H && xfeat == H && g.ldw == H;
-    L.xfuse = L.rowsk && (x32 || xh) && g.Npad == 4 * H && !(tune_str("LSTM_XFUSE") && atoi(tune_str("LSTM_XFUSE")) == 0);
+    L.xfuse = L.rowsk && (x32 || xh) && g.Npad == 4 * H && tune_on("LSTM_XFUSE");
     if (L.xfuse) {
       // the packed W_ih re-ordered to MFMA B-fragment order ([4H][64] with K = 32 zero padded: in its first 4H x 32 slots)
       int32_t* tab = nullptr;
@@ -172,7 +172,7 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
         r.xin = r.wpk_x = r.bias = b.none();
         if (L.xfuse) { r.xin = x; r.wpk_x = g.w; r.bias = g.bias; r.xfeat = L.xf; }
         r.hd = r.seed = b.none();
-        if (l == 0 && keep < 1.f && !(tune_str("LSTM_DROPFUSE") && atoi(tune_str("LSTM_DROPFUSE")) == 0)) {   // dropout applied while h_t is stored
+        if (l == 0 && keep < 1.f && tune_on("LSTM_DROPFUSE")) {   // dropout applied while h_t is stored
           L.hd_fused = b.ws(L.nm + ".hd", (int64_t)TP * rows * H, adt);
           r.hd = L.hd_fused; r.seed = io_seed; r.keep = keep; r.drop_layer = lid;
           L.dropfused = true;
@@ -277,7 +277,7 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
   if (cfg.training) {
     // lane of the weight-gradient GEMMs: 1 = second stream (api.hip: issued behind the first recurrence kernel of the phase, joined in front of
     // the UNPACK); only when the recurrences are single launches (the per-frame GRU / fp32 formulation has no OP_LSTM_BWD to fork at)
-    int wg_lane = (!gru && adt == DT_BF16 && !(tune_str("FSN_LANES") && atoi(tune_str("FSN_LANES")) == 0)) ? 1 : 0;
+    int wg_lane = (!gru && adt == DT_BF16 && tune_on("FSN_LANES")) ? 1 : 0;
     // data parallel (cfg.grad_buckets >= 2): the sub-band model's weight gradients keep the second lane busy for ~12 ms after the main stream
     // is through (profiles/r03_tuning_notes.md section 8) - the full-band model's gradients (the FRONT of the flat arena, 2/3 of it) are
     // therefore produced ON the main stream, folded and unpacked there without waiting for the lane, and their all-reduce (started by the
@@ -368,7 +368,7 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
       // input-gradient GEMM and the NEXT layer's recurrence (343 workgroups of 48 sequences on 256 CUs: its second round leaves 2/3 of the chip idle)
       b.cur_lane = wg_lane;
       b.cur_hold = wg_hold;
-      b.wg_rounds = wg_lane ? (tune_str("FSN_WG_ROUNDS") ? atoi(tune_str("FSN_WG_ROUNDS")) : 8) : 1;   // 3 -> 8 with the job-scheduled recurrences (r05 notes): 57.1 -> 56.6 ms
+      b.wg_rounds = wg_lane ? 8 : 1;   // 3 -> 8 with the job-scheduled recurrences (r05 notes): 57.1 -> 56.6 ms
       RunGemm fw = L.gx;
       fw.ydt = adt;
       if (gru) set_y(fw, dgates, rows, NG * H, 0);        // the GRU's gradient slab is 3H wide (the forward slab keeps a 4th block for W_hn h + b_hn)
@@ -378,11 +378,11 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
       // over dgates instead of two (the 1536 x 128 launch for W_ih and the bias, 1.6 ms at B = 64, and its pass over the 9.6 GB gate gradients are gone)
       const int xw = fw.nseg == 1 ? (int)rup(fw.seg[0].len, 64) : 0;
       const bool cat = !gru && L.rowsk && fw.nseg == 1 && fw.seg[0].src == 0 && xw == 64 && H % 64 == 0 && rup(xw + H + 64, 256) == rup(H, 256) &&
-                       !(tune_str("FSN_WGCAT") && atoi(tune_str("FSN_WGCAT")) == 0);
+                       tune_on("FSN_WGCAT");
       // The upper layer: [h1_t | h2_{t-1}] = 2 H = 768 columns = three whole 256-wide k tiles in ONE GEMM over dgates (W_ih and W_hh apart: 384 (+ 64 ones)
       // and 384 columns = 2 + 2 tiles, a quarter of them padding, and two passes over the gate gradients); the bias comes from the ones MFMA of k tile 0
       const bool cat2 = !cat && !gru && L.rowsk && fw.nseg == 1 && fw.seg[0].src == 0 && fw.seg[0].len == H && fw.seg[0].dt == 0 && (2 * H) % 256 == 0 &&
-                        !(tune_str("FSN_WGCAT2") && atoi(tune_str("FSN_WGCAT2")) == 0) && !(tune_str("ONES_MFMA") && atoi(tune_str("ONES_MFMA")) == 0);
+                        tune_on("FSN_WGCAT2") && tune_on("ONES_MFMA");
       if (cat || cat2) {
         RunGemm fc = fw;
         fc.x[1] = L.h; fc.bstride[1] = 0; fc.tstride[1] = (int)(rows * H); fc.base[1] = 0; fc.rowlen[1] = (int)(rows * H); fc.fstride[1] = H; fc.Tin[1] = TP;
@@ -439,18 +439,18 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
     { Fsn f = fsn0(); f.in = io_gcrm; f.out = d_sbo; if (acts) f.aux = sbo; b.push(R, OP_FSN_OUT_BWD, 205).fsn = f; }
     // sub-band head: 2 outputs.  With the row-block kernels the [T x rows x H] fp32 gradient of h (4 GB written by a K = 2 GEMM, read back
     // by the recurrence) is never materialised: the kernel computes dh = d_sbo[.., 0] W_fc[0] + d_sbo[.., 1] W_fc[1] as it needs it
-    Ls1.headfuse = Ls1.rowsk && !(tune_str("LSTM_HEADFUSE") && atoi(tune_str("LSTM_HEADFUSE")) == 0);
+    Ls1.headfuse = Ls1.rowsk && tune_on("LSTM_HEADFUSE");
     Ptr dh3 = Ls1.headfuse ? b.none() : b.ws("dh3", (int64_t)TP * rs * Hs, DT_F32);       // (not even allocated then: 4.6 GB at B = 64)
     if (Ls1.headfuse) { Ls1.dyo = d_sbo; Ls1.wo = b.pptr("sb_model.fc_output_layer.weight"); }
     fc_backward(fcs, d_sbo, h3, rs, Hs, 2, 2, dh3, 204, "sb_model", Ls1.headfuse);
     // the gradient slab between the two sub-band layers ([T x rows x H]: 4.8 GB in fp32 at B = 64, written by the input-gradient GEMM and read once by
     // the row-block backward of the layer below): bf16 like every other activation gradient of the bf16 plans when nothing but that kernel
-    // reads it (the inter-layer dropout fused into it, or no dropout); SEFD_FSN_DH16=0: fp32
-    const bool dh16 = adt == DT_BF16 && Ls1.rowsk && Ls0.rowsk && (Ls0.dropfused || !(keep < 1.f)) && !(tune_str("FSN_DH16") && atoi(tune_str("FSN_DH16")) == 0);
+    // reads it (the inter-layer dropout fused into it, or no dropout); FSN_DH16=0: fp32
+    const bool dh16 = adt == DT_BF16 && Ls1.rowsk && Ls0.rowsk && (Ls0.dropfused || !(keep < 1.f)) && tune_on("FSN_DH16");
     Ptr dh2d = b.ws("dh2d", (int64_t)TP * rs * Hs, dh16 ? adt : DT_F32);
     // round 6: with the upper layer's ONE weight-gradient GEMM (cat2, 3 k tiles) starting beside the input-gradient GEMM is 0.12 ms per step better than
     // waiting for the lower layer's recurrence (54.15 vs 54.28 ms, twice, one box); FSN_HOLD=1 restores the hold
-    wg_hold = tune_str("FSN_HOLD") && atoi(tune_str("FSN_HOLD")) == 1;
+    wg_hold = tune_is("FSN_HOLD", 1);
     lstm_backward(Ls1, dh3, true, dh2d, Hs, 0, Hs, dh16 ? adt : DT_F32, 203);
     wg_hold = 0;
     if (dh16) Ls0.dhdt = adt;
@@ -473,8 +473,8 @@ Plan* build_fsn_plan(const ModelConfig& cfg) {
     }
     if (fsn_buckets) b.flush_sums(R, 997, true);         // the sub-band folds: on the lane, behind the weight gradients they fold
     // full-band weight gradients (four 80 us launches): main stream.  Two gradient buckets need them there (no wait for the lane); since round 6 always: at
-    // the end of the lane they ran 0.35 ms past the main stream, which idles beside the 8-workgroup cluster recurrences (FSN_FB_LANE=1: on the lane)
-    if (fsn_buckets || !(tune_str("FSN_FB_LANE") && atoi(tune_str("FSN_FB_LANE")) == 1)) wg_lane = 0;
+    // the end of the lane they ran 0.35 ms past the main stream, which idles beside the 8-workgroup cluster recurrences (profiles/r06_tuning_notes.md)
+    wg_lane = 0;
     Ptr dh1 = b.ws("dh1", (int64_t)TP * B * Hf, DT_F32);
     fc_backward(fcf, d_fb, h1, B, Hf, F, FP, dh1, 102, "fb_model");
     Ptr dh0d = b.ws("dh0d", (int64_t)TP * B * Hf, DT_F32);

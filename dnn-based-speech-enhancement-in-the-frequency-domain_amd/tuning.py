@@ -1,11 +1,13 @@
-"""The library's tuning table (include/sefd.h `sefd_tuning_*`, csrc/tuning.h): tile thresholds, ring depths, lane placement, ... of the planner and
-the launchers.  ONE process-wide table - filled once from the environment variable SEFD_TUNING="KNOB=value,KNOB=value" and by the calls below -
-instead of one environment variable per knob: a plan is a function of its configuration and of this table when it is built.
+"""The library's tuning table (include/sefd.h `sefd_tuning_*`, csrc/tuning.h): tile thresholds, fusions, lane placement, ... of the planner and
+the launchers.  ONE process-wide table - seeded from the environment variable SEFD_TUNING="KNOB=value,KNOB=value" (parsed once) and changed by the
+calls below - instead of one environment variable per knob: a plan is a function of its configuration and of this table when it is built; the
+launchers and the executor read theirs on every launch / run.
 
     from sefd_amd import tuning
     tuning.set("CG256_MINM", 64)          # any later Plan(...) sees it
     with tuning.scope(BN_FUSE=2): ...     # set for the block, restored afterwards
-    tuning.unset("CG256_MINM"); tuning.clear()
+    tuning.unset("CG256_MINM")
+    tuning.clear()                        # back to the pairs of SEFD_TUNING (an empty table when the variable is not set)
 
 Knobs and defaults: INTEGRATION.md section 6.  Nothing here changes results beyond floating-point summation order."""
 import contextlib

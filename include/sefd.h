@@ -216,10 +216,11 @@ int32_t sefd_plan_status(const sefd_plan* p, int32_t clear);
 int32_t sefd_plan_status_set(const sefd_plan* p);
 
 /* ---- tuning table ------------------------------------------------------------------------------------
- * The planner's and the launchers' tuning knobs (tile thresholds, ring depths, lane placement, ...: INTEGRATION.md section 6) live in ONE process-wide
- * table, not in the environment: a plan is a function of its sefd_model_config and of this table at the moment sefd_plan_create runs.  The table is
- * filled once from the single environment variable SEFD_TUNING="KNOB=value,KNOB=value" (read the first time the table is consulted) and by these
- * calls.  value NULL unsets a knob; sefd_tuning_get returns NULL for a knob that is not set (then the built-in default applies).  The reference has
+ * The planner's and the launchers' tuning knobs (tile thresholds, fusions, lane placement, ...: INTEGRATION.md section 6) live in ONE process-wide
+ * table, not in the environment: a plan is a function of its sefd_model_config and of this table at the moment sefd_plan_create runs; launch- and
+ * run-time knobs are read on every launch / run.  The table starts from the single environment variable SEFD_TUNING="KNOB=value,KNOB=value" (parsed
+ * once, the first time the table is consulted) and is changed by these calls.  value NULL unsets a knob; sefd_tuning_get returns NULL for a knob that
+ * is not set (then the built-in default applies); sefd_tuning_clear returns the table to the pairs of SEFD_TUNING (empty when it is not set).  The reference has
  * no counterpart (its behaviour is fixed by config.py); nothing here changes results beyond floating-point summation order. */
 void sefd_tuning_set(const char* knob, const char* value);
 const char* sefd_tuning_get(const char* knob);

@@ -10,7 +10,7 @@ if [ "$REV" = WORK ]; then mkdir -p $T/$PKG && cp -r $PKG/csrc $T/$PKG/ && cp -r
 for ov in "$@"; do f=${ov%@*}; r=${ov#*@}; git show $r:$PKG/csrc/$f > $T/$PKG/csrc/$f; done
 cd $T/$PKG/csrc
 objs=""
-for s in *.hip plan*.cpp; do /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $AB_FLAGS -c -o $s.o $s & objs="$objs $s.o"; done
+for s in *.hip *.cpp; do /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $AB_FLAGS -c -o $s.o $s & objs="$objs $s.o"; done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o $OLDPWD/$OUT $objs 2>/dev/null || /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o $OUT $objs
 cd - > /dev/null; rm -rf $T; ls -la $OUT
