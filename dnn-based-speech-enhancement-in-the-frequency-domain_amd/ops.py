@@ -115,7 +115,7 @@ def _loss_bwd(ctx, g):
     est, tgt = ctx.saved_tensors
     e2 = est.float().contiguous().view(-1, est.shape[-1])
     t2 = tgt.float().contiguous().view(-1, tgt.shape[-1])
-    _, ws = loss_forward(ctx.kind, e2, t2)          # three inner products per row: recomputed rather than carried through the dispatcher
+    _, ws = loss_forward(ctx.kind, e2, t2)          # five sums per row: recomputed rather than carried through the dispatcher
     ge, gt = loss_backward(ctx.kind, e2, t2, ws, g.float().contiguous().view(1), ctx.needs_input_grad[1], ctx.needs_input_grad[2])
     return None, (ge.view(est.shape) if ctx.needs_input_grad[1] else None), (gt.view(tgt.shape) if ctx.needs_input_grad[2] else None)
 

@@ -1,6 +1,6 @@
 """Loss surface of the reference's tools_for_loss.py (:17-94) on the fused HIP reductions.
 
-Each loss is ONE pass over est/target (three inner products per utterance), a one-workgroup finalize and - for the
+Each loss is ONE pass over est/target (three inner products and the element-wise error sums per utterance), a one-workgroup finalize and - for the
 backward - one elementwise kernel `grad = ca[b]*est + cb[b]*target`.  Same call signatures and argument order as the
 reference (`sdr(s1, s2)`, `si_snr(s1, s2)`, `si_sdr(reference, estimation)`); cuda fp32 tensors only.
 """

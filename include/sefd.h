@@ -115,7 +115,10 @@ int32_t sefd_plan_run_timed(const sefd_plan* p, int phase, void* const* arenas, 
 
 /* ---- losses (tools_for_loss.py:17-94, models.py:315-323) ---------------------------------------
  * est, tgt: fp32 [B][L] device.  ws: fp32 device scratch of sefd_loss_ws_floats(B) floats.
- * forward writes the scalar loss to loss_out[0]; backward writes grad_est[B][L] = d(loss)/d(est) * grad_scale[0]. */
+ * forward writes the scalar loss to loss_out[0]; backward writes grad_est[B][L] = d(loss)/d(est) * grad_scale[0] (grad_scale NULL: 1).
+ * Both return -1, and launch nothing, for a kind outside SEFD_LOSS_MSE .. SEFD_LOSS_SISDR or B < 1 or L < 1.
+ * est and tgt need 4-byte alignment only: rows are read as float4 when L % 4 == 0 and both base pointers are 16-byte aligned, element by
+ * element otherwise (same result, lower bandwidth). */
 int64_t sefd_loss_ws_floats(int32_t B);
 int32_t sefd_loss_forward(int kind, const float* est, const float* tgt, int32_t B, int32_t L, float* ws, float* loss_out, void* stream);
 int32_t sefd_loss_backward(int kind, const float* est, const float* tgt, int32_t B, int32_t L, const float* ws,
