@@ -85,7 +85,10 @@ __device__ __forceinline__ void report_timeout(int* status, int* dstatus, int bu
 // Buffers may be batch-major [row][T][..] (DCCRN / CRN) or time-major [T][row][..] (FullSubNet, d.tmajor).
 constexpr int kMaxMT = 8;
 
-template <int H, bool PF>
+// DIR: some group of the launch walks the frames backwards (LstmRec::rev_mask, the reverse direction of a bidirectional layer): logical step s
+// of such a group is physical frame T - 1 - s in EVERY frame index below (gx prefetch, gather of the previous step's h, the c / gates / h stores,
+// the PF form's next-tile prefetch); the hand-off protocol is the same.  DIR = false compiles to the code without a direction.
+template <int H, bool PF, bool DIR = false>
 __global__ __launch_bounds__(256) void lstm_fwd_cluster_kernel(const LstmRec d, const ArenaBases ab, const int MT, int* status, int* dstatus) {
   constexpr int KS = H / 32;
   constexpr int HAS = H + 8, HCPR = H / 8, HNCH = (16 * HCPR + 255) / 256;      // cooperative gather tile: row stride, chunks per row / thread
@@ -96,6 +99,8 @@ __global__ __launch_bounds__(256) void lstm_fwd_cluster_kernel(const LstmRec d, 
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j = blockIdx.x, b0 = blockIdx.y * 16 * MT, g = blockIdx.z;
   const int64_t rstr = d.tmajor ? 1 : T, tstr = d.tmajor ? d.B : 1;       // row / frame strides, in rows
+  const bool rev = DIR && ((d.rev_mask >> g) & 1);
+  auto fr = [&](int s) -> int { if constexpr (DIR) return rev ? T - 1 - s : s; else return s; };      // logical step -> physical frame
   const float* whh = reinterpret_cast<const float*>(rp(ab, d.whh[g % d.nset]));
   const float* gx = reinterpret_cast<const float*>(rp(ab, d.gx)) + d.gx_goff[g];
   const int64_t GBT = (int64_t)d.B * T;
@@ -134,7 +139,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_cluster_kernel(const LstmRec d, 
     if (tb > 0) {
       float cc[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { bool v; const int64_t b = cell_row(mt, r, v); cc[r] = cs[(b * rstr + (int64_t)(tb - 1) * tstr) * H + unit]; }
+      for (int r = 0; r < 4; ++r) { bool v; const int64_t b = cell_row(mt, r, v); cc[r] = cs[(b * rstr + (int64_t)(tb - 1) * tstr) * H + unit]; }   // (tb == 0 in a launch with a reversed group)
       c0 = make_float4(cc[0], cc[1], cc[2], cc[3]);
     }
     cst[w][mt][lane] = c0;
@@ -149,7 +154,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_cluster_kernel(const LstmRec d, 
     for (int r = 0; r < 4; ++r) {
       bool v;
       const int64_t b = cell_row(pmt, r, v);
-      dst[r] = *reinterpret_cast<const float4*>(gx + (b * rstr + (int64_t)pt * tstr) * gx_ld + gate_col(0, unit));
+      dst[r] = *reinterpret_cast<const float4*>(gx + (b * rstr + (int64_t)fr(pt) * tstr) * gx_ld + gate_col(0, unit));
     }
     if (pt < te - 1 || pmt < MT - 1) { if (++pmt == MT) { pmt = 0; ++pt; } }      // the last prefetches re-read the last tile
   };
@@ -163,7 +168,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_cluster_kernel(const LstmRec d, 
       int nt = t, nmt = mt + 1;
       if (nmt == MT) { nmt = 0; ++nt; }
       if (nt < te && nt > 0) {
-        const auto r = hres(nt - 1);
+        const auto r = hres(fr(nt - 1));
         const uint32_t o = a_off(nmt);
 #pragma unroll
         for (int i = 0; i < KS; ++i) an[i] = __builtin_amdgcn_raw_buffer_load_b128(r, o + 64u * i, 0, kSc1);
@@ -190,7 +195,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_cluster_kernel(const LstmRec d, 
       if constexpr (!PF) {
         // the 16 x H tile of h_{t-1} is gathered once per workgroup (thread i: chunks i, i + 256, ...: whole lines, a quarter of the loads and
         // checks per wave), shared through a ping-pong LDS tile - see the backward kernel
-        const auto rs = hres(t - 1);
+        const auto rs = hres(fr(t - 1));
         uint16_t* at = htile + hpar * 16 * HAS;
         u32x4 ch[HNCH];
         uint32_t off[HNCH];
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_cluster_kernel(const LstmRec d, 
         for (int ks = 0; ks < KS; ++ks) a[ks] = *reinterpret_cast<const u32x4*>(at + (lane & 15) * HAS + 32 * ks + 8 * kq);
         hpar ^= 1;
       } else {
-        if (!have) gather<KS>(hres(t - 1), a_off(mt), 64u, a, budget);
+        if (!have) gather<KS>(hres(fr(t - 1)), a_off(mt), 64u, a, budget);
       }
       issue_next(t, mt);
 #pragma unroll
@@ -250,7 +255,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_cluster_kernel(const LstmRec d, 
         bool v;
         const int64_t b = cell_row(mt, r, v);
         if (v) {
-          const int64_t so = (b * rstr + (int64_t)t * tstr) * H + unit;
+          const int64_t so = (b * rstr + (int64_t)fr(t) * tstr) * H + unit;
           *reinterpret_cast<float4*>(gates + so * 4) = make_float4(ig[k], fg[k], gg[k], og[k]);
           cs[so] = cn[k];
         }
@@ -263,7 +268,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_cluster_kernel(const LstmRec d, 
     if (lane < 32) {
       const u32x4 v = *reinterpret_cast<const u32x4*>(stg + srow * 16 + 8 * shalf);
       const int b = b0 + 16 * mt + srow;
-      if (b < d.B) __builtin_amdgcn_raw_buffer_store_b128(v, hres(t), (uint32_t)(((int64_t)b * rstr * H + ubase + 8 * shalf) * 2), 0, kSc1);
+      if (b < d.B) __builtin_amdgcn_raw_buffer_store_b128(v, hres(fr(t)), (uint32_t)(((int64_t)b * rstr * H + ubase + 8 * shalf) * 2), 0, kSc1);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -286,7 +291,8 @@ __global__ __launch_bounds__(256) void lstm_fwd_cluster_kernel(const LstmRec d, 
 // --------------------------------------------------------------------------------------------------------------- backward
 // Tile (t, mt), frames last to first: dh_rec = dgates_{t+1}[tile] . W_hh (gathered first: the peers stored it MT tiles ago),
 // then the cell backward of frame t, whose dgates_t leave write-through for the peers' (and this wave's) tile (t-1, mt).
-template <int H>
+// DIR as in the forward: a reversed group's logical step s (walked T - 1 .. 0 here) is physical frame T - 1 - s, its "previous" cell state the next physical frame.
+template <int H, bool DIR = false>
 __global__ __launch_bounds__(256) void lstm_bwd_cluster_kernel(const LstmRec d, const ArenaBases ab, const int MT, int* status, int* dstatus) {
   constexpr int KS = 4 * H / 32;                 // k32 steps over the 4H gate columns
   constexpr int AS = 4 * H + 8, CPR = 4 * H / 8, NCH = 16 * CPR / 256;   // LDS tile row stride, 16-byte chunks per row, chunks per thread
@@ -298,6 +304,8 @@ __global__ __launch_bounds__(256) void lstm_bwd_cluster_kernel(const LstmRec d, 
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j = blockIdx.x, b0 = blockIdx.y * 16 * MT, g = blockIdx.z;
   const int64_t rstr = d.tmajor ? 1 : T, tstr = d.tmajor ? d.B : 1;
+  const bool rev = DIR && ((d.rev_mask >> g) & 1);
+  auto fr = [&](int s) -> int { if constexpr (DIR) return rev ? T - 1 - s : s; else return s; };
   const int64_t GBT = (int64_t)d.B * T;
   const float* whh = reinterpret_cast<const float*>(rp(ab, d.whh[g % d.nset]));
   const float* gates = reinterpret_cast<const float*>(rp(ab, d.gates)) + (int64_t)g * GBT * H * 4;
@@ -339,10 +347,11 @@ __global__ __launch_bounds__(256) void lstm_bwd_cluster_kernel(const LstmRec d, 
     for (int r = 0; r < 4; ++r) {
       bool v;
       const int64_t b = cell_row(pmt, r, v);
-      const int64_t o = (b * rstr + (int64_t)pt * tstr) * H + unit;
+      const int64_t o = (b * rstr + (int64_t)fr(pt) * tstr) * H + unit;
       s.g[r] = *reinterpret_cast<const float4*>(gates + o * 4);
       s.ct[r] = cs[o];
-      s.cp[r] = pt > 0 ? cs[o - tstr * H] : 0.f;
+      if constexpr (DIR) s.cp[r] = pt > 0 ? (rev ? cs[o + tstr * H] : cs[o - tstr * H]) : 0.f;      // the previous logical step's cell state
+      else s.cp[r] = pt > 0 ? cs[o - tstr * H] : 0.f;
       s.dh[r] = dh[o];
     }
     if (pt > 0 || pmt < MT - 1) { if (++pmt == MT) { pmt = 0; --pt; } }
@@ -355,7 +364,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_cluster_kernel(const LstmRec d, 
       // The 16 x 4H tile of dgates_{t+1} is gathered ONCE per workgroup: thread i takes the 16-byte chunks i, i + 256, ... (whole lines,
       // a quarter of the tile and of the validity checks per wave instead of all of it), re-reads them until none holds an unwritten
       // half-word, and puts them into the LDS tile; after the barrier every wave reads its A fragments from there.
-      const auto r = gres(t + 1);
+      const auto r = gres(fr(t + 1));
       uint16_t* at = atile + (DB ? par * 16 * AS : 0);
       u32x4 ch[NCH];
       uint32_t off[NCH];
@@ -424,7 +433,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_cluster_kernel(const LstmRec d, 
     __builtin_amdgcn_wave_barrier();
     {
       // dgates_t of this wave: 16 sequences x (16 units x 4 gates) = 16 x 128 bytes = 128 chunks of 16 bytes, two per lane
-      const auto r = gres(t);
+      const auto r = gres(fr(t));
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int cidx = lane + 64 * i, row = cidx >> 3, piece = cidx & 7;
@@ -493,20 +502,41 @@ static int* cluster_status_word() {
   return w;
 }
 
-template <int H>
+template <int H, bool DIR>
 static void launch_c(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd) {
   int* status = ab.status ? ab.status : cluster_status_word();      // the issuing plan's word (api.hip plan_run)
   const int mt = pick_mt(d, H / 64);
   const dim3 grid(H / 64, (d.B + 16 * mt - 1) / (16 * mt), d.G);
   if (fwd) {
-    if constexpr (H <= 384) { if (mt > 1) { hipLaunchKernelGGL((lstm_fwd_cluster_kernel<H, true>), grid, dim3(256), 0, st, d, ab, mt, status, ab.dstatus); return; } }
-    hipLaunchKernelGGL((lstm_fwd_cluster_kernel<H, false>), grid, dim3(256), 0, st, d, ab, mt, status, ab.dstatus);
+    if constexpr (H <= 384) { if (mt > 1) { hipLaunchKernelGGL((lstm_fwd_cluster_kernel<H, true, DIR>), grid, dim3(256), 0, st, d, ab, mt, status, ab.dstatus); return; } }
+    hipLaunchKernelGGL((lstm_fwd_cluster_kernel<H, false, DIR>), grid, dim3(256), 0, st, d, ab, mt, status, ab.dstatus);
   } else {
-    hipLaunchKernelGGL((lstm_bwd_cluster_kernel<H>), grid, dim3(256), 0, st, d, ab, mt, status, ab.dstatus);
+    hipLaunchKernelGGL((lstm_bwd_cluster_kernel<H, DIR>), grid, dim3(256), 0, st, d, ab, mt, status, ab.dstatus);
+  }
+}
+
+__global__ void lstm_cluster_refuse_kernel(int* host_word, int* dev_word) { set_status(host_word, dev_word); }
+
+template <bool DIR>
+static void launch_h(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd) {
+  switch (d.H) {
+    case 192: launch_c<192, DIR>(d, ab, st, fwd); break;
+    case 256: launch_c<256, DIR>(d, ab, st, fwd); break;
+    case 320: launch_c<320, DIR>(d, ab, st, fwd); break;
+    case 384: launch_c<384, DIR>(d, ab, st, fwd); break;
+    case 448: launch_c<448, DIR>(d, ab, st, fwd); break;
+    default: launch_c<512, DIR>(d, ab, st, fwd); break;
   }
 }
 
 void launch_lstm_cluster(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd) {
+  // a reversed group resumes from no saved state: its launch covers the whole sequence (t0 = t1 = 0), of at most 4 groups (gx_goff).  Anything else is
+  // not launched; the plan's status word says so (as after a kernel that gave up)
+  const int mask = d.rev_mask & ((1 << (d.G < 4 ? d.G : 4)) - 1);
+  if (mask != 0 && (d.t0 != 0 || d.t1 != 0 || d.G > 4 || !lstm_cluster_supported(d.H))) {
+    hipLaunchKernelGGL(lstm_cluster_refuse_kernel, dim3(1), dim3(1), 0, st, ab.status ? ab.status : cluster_status_word(), ab.dstatus);
+    return;
+  }
   // the exchanged arrays start out "unwritten": the frames of h this launch produces, all of dgates before the backward
   if (fwd) {
     const int t0 = d.t0, t1 = d.t1 > 0 ? d.t1 : d.T;
@@ -520,14 +550,8 @@ void launch_lstm_cluster(const LstmRec& d, const ArenaBases& ab, hipStream_t st,
     const int64_t n = hi + ((int64_t)d.B * d.T - 1) * d.gx_ld + 4 * d.H;
     (void)hipMemsetD16Async((hipDeviceptr_t)rp(ab, d.dgates), 0xffff, (size_t)n, st);
   }
-  switch (d.H) {
-    case 192: launch_c<192>(d, ab, st, fwd); break;
-    case 256: launch_c<256>(d, ab, st, fwd); break;
-    case 320: launch_c<320>(d, ab, st, fwd); break;
-    case 384: launch_c<384>(d, ab, st, fwd); break;
-    case 448: launch_c<448>(d, ab, st, fwd); break;
-    default: launch_c<512>(d, ab, st, fwd); break;
-  }
+  if (mask != 0) launch_h<true>(d, ab, st, fwd);
+  else launch_h<false>(d, ab, st, fwd);
 }
 
 }  // namespace sefd

@@ -196,6 +196,7 @@ void finish_plan(Builder& b, Plan* P, int64_t nparam, int64_t nstate) {
 }
 
 Plan* build_plan(const ModelConfig& cfg) {
+  if (cfg.model == 6) return build_seq_plan(cfg);
   if (cfg.model == 5) return build_torchistft_plan(cfg);
   if (cfg.model == 4) return build_torchstft_plan(cfg);
   if (cfg.model == 3) return build_fsn_plan(cfg);

@@ -11,7 +11,7 @@
 //
 // This header: what every planner shares - the front-end geometry (Stft) and the Builder (arenas, parameter tables, op list, GEMM
 // descriptors, the conv stack, the recurrent block, weight gradients and their UNPACK).  The planners: plan_dccrn.cpp, plan_crn.cpp,
-// plan_fsn.cpp, plan_frontend.cpp; the post-pass over a finished plan and build_plan(): plan.cpp.
+// plan_fsn.cpp, plan_seq.cpp, plan_frontend.cpp; the post-pass over a finished plan and build_plan(): plan.cpp.
 #pragma once
 #include "plan.h"
 #include "tuning.h"
@@ -906,6 +906,7 @@ void finish_plan(Builder& b, Plan* P, int64_t nparam, int64_t nstate);
 
 Plan* build_frontend_plan(const ModelConfig& cfg);
 Plan* build_fsn_plan(const ModelConfig& cfg);
+Plan* build_seq_plan(const ModelConfig& cfg);
 Plan* build_torchstft_plan(const ModelConfig& cfg);
 Plan* build_torchistft_plan(const ModelConfig& cfg);
 

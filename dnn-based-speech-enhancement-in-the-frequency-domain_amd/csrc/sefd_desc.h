@@ -242,7 +242,10 @@ struct LstmRec {
   // fused - gate pre-activations = bias (b_ih + b_hh, fp32 [4H] unit-major) + x_t . W_ih^T (xin bf16 [T][rows][32], wpk_x packed like
   // wpk_f with ONE k-step: rows_wf_index(32, c, k)) + h_{t-1} . W_hh^T; `gx` is not read (no 8 GB pre-activation slab to write and re-read)
   Ptr xin, wpk_x, bias;
-  int32_t xfeat, pad3_;
+  int32_t xfeat;
+  int32_t rev_mask;            // cluster kernels (lstm_cluster.hip) only, formerly a pad word: bit g set = group g walks the frames backwards, logical step s =
+                               // physical frame T - 1 - s (the reverse direction of a bidirectional layer beside the forward one: G = 2, mask 0b10).  Such a
+                               // launch covers the whole sequence (t0 = t1 = 0); 0 in every plan that has no direction
   // impl 1, forward, hd != A_NONE: the inverted dropout that follows the layer (struct Dropout: seed, keep, layer) is applied while h_t is
   // stored - hd [T][rows][H] (dtype hdt) = h * scale, no separate pass over the 2 GB h array
   // backward, seed != A_NONE: `dh` is the gradient w.r.t. the DROPPED h: it is multiplied by the same mask as it is loaded

@@ -609,18 +609,96 @@ class CRN(_SefdModule):
 
 
 # ------------------------------------------------------------------------------------------ FullSubNet (models.py:568-682)
-class SequenceModel(nn.Module):
-    """Parameter holder (tools_for_model.py:726-777): 2-layer nn.LSTM or nn.GRU (dropout=0.8) + Linear (+ activation)."""
+class _SeqFunction(torch.autograd.Function):
+    """One SequenceModel plan (csrc/plan_seq.cpp) at its time-major boundary: x [T, B, IP] -> pre-activation y [T, B, O]."""
+
+    @staticmethod
+    def forward(ctx, owner, rt, xt, *params):
+        plan, ar = rt
+        T, B, IP = xt.shape
+        plan.io(ar, "x", (T, B, IP)).copy_(xt)
+        plan.view(ar, "io.seed").view(torch.int32)[:1].add_(1)        # fresh dropout masks every forward (device-side counter)
+        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
+        plan.stamp = getattr(plan, "stamp", 0) + 1
+        ctx.owner, ctx.rt, ctx.shape, ctx.stamp = owner, rt, (T, B, IP), plan.stamp
+        return plan.io(ar, "y", (T, B, plan.NF_out)).clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        plan, ar = ctx.rt
+        if ctx.stamp != plan.stamp:
+            raise RuntimeError("sefd: a later forward of the same shape overwrote the activations this backward needs")
+        T, B, IP = ctx.shape
+        plan.io(ar, "grad_y", (T, B, plan.NF_out)).copy_(g)
+        plan.run(PHASE_BWD, ar, torch.cuda.current_stream().cuda_stream)
+        flat = ctx.owner._flat_grad.clone()
+        return (None, None, plan.io(ar, "grad_x", (T, B, IP)).clone()) + tuple(flat[off:off + n].view(shape) for (off, n, shape) in ctx.owner._param_slices)
+
+
+class SequenceModel(_SefdModule):
+    """Same constructor and state_dict as the reference (tools_for_model.py:726-795): nn.LSTM or nn.GRU of any depth, optionally bidirectional
+    (dropout=0.8 between the layers), + Linear (+ activation).  As a child of FullSubNet it is a parameter holder: FullSubNet owns the flat arenas
+    and plans both of its SequenceModels itself.  On its own, `forward` runs the SequenceModel plan (csrc/plan_seq.cpp)."""
+
+    _ACTS = {None: None, "None": None, "": None, "Tanh": torch.tanh, "ReLU": torch.relu, "ReLU6": nn.functional.relu6}
 
     def __init__(self, input_size, output_size, hidden_size, num_layers, bidirectional, sequence_model="LSTM", output_activate_function="Tanh"):
         super().__init__()
-        if sequence_model not in ("LSTM", "GRU") or bidirectional or num_layers != 2:
-            raise NotImplementedError("only the 2-layer unidirectional LSTM / GRU SequenceModel is on the HIP path")
+        if sequence_model not in ("LSTM", "GRU"):
+            raise NotImplementedError(f"Not implemented {sequence_model}")
+        if output_activate_function not in self._ACTS:
+            raise NotImplementedError(f"Not implemented activation function {output_activate_function}")
         rnn = nn.LSTM if sequence_model == "LSTM" else nn.GRU
         self.sequence_model = rnn(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers, batch_first=True,
-                                  bidirectional=False, dropout=0.8)
-        self.fc_output_layer = nn.Linear(hidden_size, output_size)
+                                  bidirectional=bool(bidirectional), dropout=0.8)
+        self.fc_output_layer = nn.Linear(hidden_size * (2 if bidirectional else 1), output_size)
         self.output_activate_function = output_activate_function
+        self._seq = dict(input_size=int(input_size), output_size=int(output_size), hidden_size=int(hidden_size), num_layers=int(num_layers),
+                         bidirectional=bool(bidirectional), sequence_model=sequence_model)
+        self.dropout_keep = 0.2                      # nn.LSTM(dropout=0.8), as FullSubNet.dropout_keep; eval mode: no dropout
+        self.act_dtype = cfg.act_dtype
+        self._init_runtime_state()                   # (a FullSubNet parent re-tags the parameters as its own afterwards)
+
+    def _seq_runtime(self, B, T, device):
+        if not self._flat_ok(device):
+            self._flatten(device)
+        keep = self.dropout_keep if self.training else 1.0
+        key = ("seq", B, T, bool(self.training), keep, self.act_dtype)
+        rt = self._runtimes.get(key)
+        if rt is None:
+            # a training-capable plan in eval mode too (keep = 1): inside a larger network the input gradient is needed in either mode
+            plan = Plan(B, T, act_dtype=self.act_dtype, training=True, model="SequenceModel", seq=dict(self._seq, keep=keep))
+            plan.owner = weakref.ref(self)
+            plan.NF_out = self._seq["output_size"]
+            assert [n for n, _ in self._trainable()] == list(plan.params.keys()), "parameter order differs from the plan"
+            assert [s[0] for s in self._param_slices] == [v[0] for v in plan.params.values()]
+            ar = [None] * ARENA_COUNT
+            ar[ARENA_WS] = torch.zeros(max(plan.arena_bytes[ARENA_WS], 256), dtype=torch.uint8, device=device)
+            ar[ARENA_CONST] = torch.from_numpy(plan.const_image()).to(device)
+            ar[ARENA_IO] = torch.zeros(plan.arena_bytes[ARENA_IO], dtype=torch.uint8, device=device)
+            ar[ARENA_PARAM], ar[ARENA_GRAD], ar[ARENA_STATE] = self._flat_param, self._flat_grad, self._flat_state
+            rt = (plan, ar)
+            self._runtimes[key] = rt
+        return rt
+
+    def forward(self, x):
+        """tools_for_model.py:779-795: x [B, F, T] -> [B, O, T]."""
+        assert x.dim() == 3
+        if not x.is_cuda:
+            raise RuntimeError("sefd SequenceModel runs on the MI355X only (cuda tensors); there is no CPU fallback")
+        B, I, T = x.shape
+        assert I == self._seq["input_size"], f"{self.__class__.__name__}: expected {self._seq['input_size']} input features, got {I}"
+        rt = self._seq_runtime(B, T, x.device)
+        # The [B, F, T] <-> time-major permute / pad and the output activation are element-wise torch at the plan's boundary: O(B * (I + O) * T)
+        # values beside the recurrences' O(B * T * H * H) work.  Autograd carries the gradient through them.
+        xt = x.float().permute(2, 0, 1)
+        if I % 8:
+            xt = nn.functional.pad(xt, (0, 8 - I % 8))                # IP = roundup(I, 8): zero pad columns
+        y = _SeqFunction.apply(self, rt, xt.contiguous(), *[p for _, p in self._trainable()])
+        act = self._ACTS[self.output_activate_function]
+        if act is not None:
+            y = act(y)
+        return y.permute(1, 2, 0).contiguous()
 
 
 def _weight_init(m):

@@ -21,12 +21,12 @@ class Plan:
     def __init__(self, B, L, kernel_num=(32, 64, 128, 256, 256, 256), rnn_layers=2, rnn_units=256, win_len=400,
                  win_inc=100, fft_len=512, masking_mode="E", lstm="complex", skip_type=True, act_dtype="fp32",
                  kernel_size=5, training=True, model="DCCRN", fsn=None, bn_world=1, grad_buckets=1, use_cbn=False, win_type="hanning",
-                 cbn_sync=False):
+                 cbn_sync=False, seq=None):
         self.lib = _lib.lib()
         if masking_mode not in MASK_MODES:
             raise NotImplementedError(f"masking_mode {masking_mode!r} is not on the HIP path yet")
         cfg = _lib.ModelConfig()
-        cfg.model = {"DCCRN": 0, "CRN": 1, "STFT": 2, "FullSubNet": 3, "TorchSTFT": 4, "TorchISTFT": 5}[model]
+        cfg.model = {"DCCRN": 0, "CRN": 1, "STFT": 2, "FullSubNet": 3, "TorchSTFT": 4, "TorchISTFT": 5, "SequenceModel": 6}[model]
         cfg.B, cfg.L = int(B), int(L)
         if model == "FullSubNet":
             # L = number of STFT frames T; kernel_num carries (sb_neighbors, fb_neighbors, look_ahead, fb_hidden, sb_hidden,
@@ -38,8 +38,18 @@ class Plan:
             kernel_num = (f["sb_num_neighbors"], f["fb_num_neighbors"], f["look_ahead"], f["fb_hidden"], f["sb_hidden"],
                           acts[f["fb_act"]], acts[f["sb_act"]], int(round(f["keep"] * 1000)),
                           {"LSTM": 0, "GRU": 1}[f["sequence_model"]], FSN_NORMS[f["norm_type"]])
+        if model == "SequenceModel":
+            # B = number of sequences, L = frames T; kernel_num carries (input size, output size, hidden size, num_layers, bidirectional,
+            #                                                            0 LSTM / 1 GRU, dropout keep probability in 1/1000) - csrc/plan_seq.cpp
+            s = dict(input_size=257, output_size=257, hidden_size=512, num_layers=2, bidirectional=False, sequence_model="LSTM", keep=0.2)
+            s.update(seq or {})
+            if s["sequence_model"] not in ("LSTM", "GRU"):
+                raise NotImplementedError(f"Not implemented {s['sequence_model']}")
+            kernel_num = (s["input_size"], s["output_size"], s["hidden_size"], s["num_layers"], 1 if s["bidirectional"] else 0,
+                          {"LSTM": 0, "GRU": 1}[s["sequence_model"]], int(round(s["keep"] * 1000)))
+            self.seq = s
         cfg.win_len, cfg.hop, cfg.fft_len = win_len, win_inc, fft_len
-        cfg.n_layers = len(kernel_num) if model != "FullSubNet" else 0
+        cfg.n_layers = len(kernel_num) if model not in ("FullSubNet", "SequenceModel") else 0
         for i, k in enumerate(kernel_num):
             cfg.kernel_num[i] = int(k)
         cfg.rnn_layers, cfg.rnn_units = rnn_layers, rnn_units

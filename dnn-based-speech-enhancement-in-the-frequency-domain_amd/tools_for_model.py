@@ -9,6 +9,14 @@ from . import _lib
 from . import config as cfg
 from .plan import PHASE_FWD, Plan
 
+
+def __getattr__(name):
+    # tools_for_model.SequenceModel (tools_for_model.py:726-795) is models.SequenceModel: resolved on first use, models.py imports this module
+    if name == "SequenceModel":
+        from .models import SequenceModel
+        return SequenceModel
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
 _FE_CACHE = {}
 
 

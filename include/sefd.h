@@ -23,13 +23,16 @@ typedef struct sefd_plan sefd_plan;
 
 /* Mirror of the config.py knobs that shape DCCRN (config.py:35-68) plus batch geometry. */
 typedef struct sefd_model_config {
-  int32_t model;          /* 0 DCCRN, 1 CRN, 2 ConvSTFT front end, 3 FullSubNet, 4 torch.stft front end, 5 torch.istft (see build_plan, csrc/plan.cpp) */
+  int32_t model;          /* 0 DCCRN, 1 CRN, 2 ConvSTFT front end, 3 FullSubNet, 4 torch.stft front end, 5 torch.istft,
+                             6 SequenceModel on its own (see build_plan, csrc/plan.cpp) */
   int32_t B, L;           /* batch, samples per clip */
   int32_t win_len, hop, fft_len;
   int32_t n_layers;
   int32_t kernel_num[12]; /* cfg.dccrn_kernel_num; FullSubNet (model 3): sb/fb neighbours (each 0 .. 31), look_ahead, fb/sb hidden,
                              fb/sb output activation (0 None, 1 ReLU, 2 Tanh, 3 ReLU6), dropout keep in 1/1000, [8] sequence model (0 LSTM, 1 GRU), [9] norm type (0 offline_laplace_norm,
-                             1 cumulative_laplace_norm, 2 offline_gaussian_norm, 3 cumulative_layer_norm) */
+                             1 cumulative_laplace_norm, 2 offline_gaussian_norm, 3 cumulative_layer_norm);
+                             SequenceModel (model 6; B = sequences, L = frames T): input size, output size, hidden size (multiple of 8), num_layers (1 .. 8), bidirectional,
+                             sequence model (0 LSTM, 1 GRU), dropout keep in 1/1000.  I/O, time-major fp32: x [T][B][roundup(I, 8)] -> y [T][B][O]; grad_y -> grad_x */
   int32_t rnn_layers, rnn_units;
   int32_t mask_mode;      /* 0 'E', 1 'C', 2 'R' (cfg.masking_mode) */
   int32_t lstm_complex;   /* cfg.lstm == 'complex' */
