@@ -729,6 +729,7 @@ __global__ void ola_fwd_kernel(const Ola d, const ArenaBases ab) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t b = i / d.L;
     const int p = (int)(i - b * d.L) + d.trim;
+    if (d.Lout > 0 && p - d.trim >= d.Lout) { wav[i] = 0.f; continue; }     // behind the clip ConviSTFT returns (past the normaliser table when hop > trim)
     int t1 = p / d.hop; if (t1 > d.T - 1) t1 = d.T - 1;
     int t0 = (p - d.win + d.hop) / d.hop; if (p - d.win + 1 <= 0) t0 = 0;
     float s = 0.f;
@@ -749,7 +750,7 @@ __global__ void ola_bwd_kernel(const Ola d, const ArenaBases ab) {
     const int p = (int)(i - b * Lp);
     float v = 0.f;
     const int s = p - d.trim;
-    if (s >= 0 && s < d.L) {
+    if (s >= 0 && s < (d.Lout > 0 ? d.Lout : d.L)) {
       const float w = wav[b * d.L + s];
       // clamp_ passes the gradient where the un-clamped value lies in [-1, 1]; a clamped sample equals +-1 exactly
       if (w > -1.f && w < 1.f) v = dwav[b * d.L + s] / (coff[p] + 1e-8f);

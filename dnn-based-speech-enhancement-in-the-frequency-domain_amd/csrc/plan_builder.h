@@ -20,6 +20,8 @@
 #include <array>
 #include <cassert>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 
@@ -177,10 +179,14 @@ struct Builder {
   }
   // ... reading D slices `pitch` apart instead (the [D][Cl] rows of the encoder output): `len` columns from `off` of every slice
   static void rows_slices(RunGemm& g, int D, int pitch, int off, int len) {
+    if (D > kMaxSeg) { std::fprintf(stderr, "sefd planner: rows_slices over %d > kMaxSeg runs (slice_chunks)\n", D); std::abort(); }
     g.nseg = D;
     for (int dd = 0; dd < D; ++dd) g.seg[dd] = Seg{0, 0, dd * pitch + off, len, 0};
     layout_segs(g);
   }
+  // A descriptor holds kMaxSeg runs, so a recurrent input GEMM reads the D channel slices kMaxSeg at a time: slice_chunks(D) GEMMs, every one
+  // after the first adding onto the first one's output (kRunAccum, no bias)
+  static int slice_chunks(int D) { return (D + kMaxSeg - 1) / kMaxSeg; }
   // ... writing columns [yoff, yoff + N) of the rows [B][T][ld] of y
   void rows_out(RunGemm& g, Ptr y, int ld, int yoff = 0) const {
     g.y = y; g.y_bstride = (int64_t)fe.T * ld; g.y_tstride = ld; g.y_off = yoff;
@@ -354,6 +360,7 @@ struct Builder {
     std::memset(&ola, 0, sizeof(ola));
     ola.frames = frames; ola.wav = wav; ola.coff = fe.c_coff; ola.dwav = ola.dpad = none();
     ola.B = fe.B; ola.T = fe.T; ola.L = fe.L; ola.win = fe.W; ola.hop = fe.hop; ola.trim = fe.trim;
+    if (fe.Lp - 2 * fe.trim < fe.L) ola.Lout = fe.Lp - 2 * fe.trim;      // ConviSTFT's `[..., trim:-trim]` of the frames' span (tools_for_model.py:111)
     push(ops, OP_OLA_FWD, 502).ola = ola;
     return ola;
   }
@@ -592,7 +599,8 @@ struct Builder {
   // [B][T][D][Cl] in the reference's feature order c*D + d (models.py:214-218; a weight permutation here), then a Linear into the decoder input
   struct Rnn { int D = 0, Cl = 0, H = 0; bool stepped = false; } rnn;   // stepped: one GEMM + one cell launch per frame instead of the persistent kernels
   // what the backward of a layer needs from its forward: buffers, the input GEMM with its coefficient and bias functions, W_hh
-  struct RealLstm { std::string nm; int l; RunGemm gx; Coef cgx; Bias bgx; Ptr gxb, h, gates, cst; const ParamInfo* Whh; };
+  // (gxc / cgxc: the input GEMM per chunk of channel slices with its coefficient function - one chunk unless layer 0 reads more than kMaxSeg slices)
+  struct RealLstm { std::string nm; int l; RunGemm gx; Coef cgx; Bias bgx; Ptr gxb, h, gates, cst; const ParamInfo* Whh; std::vector<RunGemm> gxc; std::vector<Coef> cgxc; };
   void real_cell(LstmCell& cl, const RealLstm& Lr, int t, bool fwd, Ptr dh, Ptr dcb, Ptr dgates) {
     const int adt = c.act_dtype, H = rnn.H, T = fe.T;
     cl.gates = mk(A_WS, Lr.gxb.off + (int64_t)t * 4 * H * 4);
@@ -628,14 +636,21 @@ struct Builder {
     Lr.gates = ws(nm + ".gates", BT * 4 * H, DT_F32);
     Lr.cst = ws(nm + ".c", BT * H, DT_F32);
     const int I = l == 0 ? D * Cl : H;
-    RunGemm g = rows_gemm(x, adt, I, 0, I, 4 * H, DT_F32);
-    if (l == 0) rows_slices(g, D, Cl, 0, Cl);
     Lr.cgx = [=](int nn, int sg, int j) -> int32_t { return pe(*Wih, (int64_t)gate_torch_row(nn, H) * I + (l == 0 ? j * D + sg : j), 1); };
     Lr.bgx = [=](int nn, int32_t* o) { o[0] = pe(*bih, gate_torch_row(nn, H), 1); o[1] = pe(*bhh, gate_torch_row(nn, H), 1); };
-    pack_weights(ops, g, Lr.cgx, nm + ".ih", tag, &Lr.bgx);
-    rows_out(g, Lr.gxb, 4 * H);
-    push(ops, OP_RUNGEMM, tag).g = g;
-    Lr.gx = g;
+    for (int ck = 0; ck < (l == 0 ? slice_chunks(D) : 1); ++ck) {
+      const int d0 = ck * kMaxSeg;
+      RunGemm g = rows_gemm(x, adt, I, 0, I, 4 * H, DT_F32);
+      if (l == 0) rows_slices(g, std::min(kMaxSeg, D - d0), Cl, d0 * Cl, Cl);
+      const Coef cf = Lr.cgx;
+      const Coef cc = ck == 0 ? cf : Coef([=](int nn, int sg, int j) -> int32_t { return cf(nn, sg + d0, j); });
+      pack_weights(ops, g, cc, nm + ".ih" + (ck ? "_" + std::to_string(ck) : ""), tag, ck == 0 ? &Lr.bgx : nullptr);
+      if (ck) g.flags |= kRunAccum;
+      rows_out(g, Lr.gxb, 4 * H);
+      push(ops, OP_RUNGEMM, tag).g = g;
+      Lr.gxc.push_back(g); Lr.cgxc.push_back(cc);
+    }
+    Lr.gx = Lr.gxc[0];
     if (!rnn.stepped) {
       real_rec(push(ops, OP_LSTM_FWD, tag).lstm, Lr, none(), none(), gdt);
       return Lr;
@@ -694,9 +709,12 @@ struct Builder {
         }
       }
     }
-    RunGemm fw = Lr.gx;
-    fw.ydt = adt;                         // WGRAD reads dy = dgates (act dtype), not the fp32 gx the forward wrote
-    wgrad(ops, fw, dgates, Lr.cgx, tag, &Lr.bgx);
+    for (size_t ck = 0; ck < Lr.gxc.size(); ++ck) {
+      RunGemm fw = Lr.gxc[ck];
+      fw.ydt = adt;                       // WGRAD reads dy = dgates (act dtype), not the fp32 gx the forward wrote
+      fw.flags &= ~kRunAccum;
+      wgrad(ops, fw, dgates, Lr.cgxc[ck], tag, ck == 0 ? &Lr.bgx : nullptr);
+    }
     RunGemm f = rows_gemm(Lr.h, adt, H, 0, H, 4 * H, adt);      // W_hh: dW[n][k] = sum_t dgates[t][n] * h[t-1][k]
     f.seg[0].dt = -1;
     rows_out(f, dgates, 4 * H);
@@ -746,8 +764,18 @@ struct Builder {
   // WGRAD for the layer whose forward descriptor is `f` (same A runs + a ones run) against upstream gradient `dy`.
   void wgrad(std::vector<Op>& ops, const RunGemm& f, Ptr dy, const Coef& coef, int tag,
              const std::function<void(int n, int32_t out[2])>* bias) {
+    if (bias && f.nseg >= kMaxSeg) {
+      // kMaxSeg data runs (a recurrent input GEMM over kMaxSeg channel slices) leave no room for the ones run: the bias gradient comes from a
+      // GEMM of its own over the same rows (the form of the mask layer's bias-only pass)
+      wgrad(ops, f, dy, coef, tag, nullptr);
+      RunGemm fb = f;
+      fb.nseg = 0;
+      const Coef none_coef = [](int, int, int) -> int32_t { return 0; };
+      wgrad(ops, fb, dy, none_coef, tag, bias);
+      return;
+    }
     RunGemm g = f;            // operands keep the forward dtype: fp32 -> 32x32x2 fp32 MFMA, bf16 -> transposing 16x16x32 bf16 MFMA
-    if (bias && g.nseg < kMaxSeg) {
+    if (bias) {
       Seg& o = g.seg[g.nseg++];
       o.src = -1; o.dt = 0; o.off = 0; o.len = 1; o.koff = 0;
     }

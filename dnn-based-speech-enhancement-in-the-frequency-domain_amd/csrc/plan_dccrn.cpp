@@ -199,7 +199,8 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
 
   // ------------------------------------------------------------------ complex LSTM stack (tools_for_model.py:141-181)
   const int64_t BT = (int64_t)B * T;
-  struct Lstm { RunGemm gx[2]; Builder::Coef cgx[2]; Builder::Bias bgx; Ptr gxb, h, gates, cst, hc; RunGemm hh[2]; };
+  // (gxc / cgxc: the input GEMM of a part per chunk of channel slices - one chunk unless layer 0 reads more than kMaxSeg slices, Builder::slice_chunks)
+  struct Lstm { RunGemm gx[2]; Builder::Coef cgx[2]; Builder::Bias bgx; Ptr gxb, h, gates, cst, hc; RunGemm hh[2]; std::vector<RunGemm> gxc[2]; std::vector<Builder::Coef> cgxc[2]; };
   std::vector<Lstm> ls(NL);
   Ptr lin = enc[n - 1].z;
   b.rnn = Builder::Rnn{D, Cl, H, stepped};
@@ -268,25 +269,33 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
     };
     ls[l].bgx = bias;
     const bool gx_merge = tune_on("GX_MERGE") && BT * 8 * H < (1LL << 31);
+    const int nck = l == 0 ? Builder::slice_chunks(D) : 1;
     for (int p = 0; p < 2; ++p) {
-      RunGemm g = b.rows_gemm(lin, adt, rowlen, p * H, H, 8 * H, DT_F32);
-      if (l == 0) Builder::rows_slices(g, D, Cl, p * (Cl / 2), Cl / 2);
       Builder::Coef coef = [=](int nn, int s, int j) -> int32_t {
         const int set = nn / (4 * H), gq = gate_torch_row(nn % (4 * H), H);
         const int feat = (l == 0) ? j * D + s : j;      // reference feature order c*D + d (models.py:203-206)
         return pe(*Wih[set], (int64_t)gq * I + feat, 1);
       };
-      b.pack_weights(F, g, coef, nm + ".ih" + std::to_string(p), 200 + l, p == 0 ? &bias : nullptr);
-      if (p == 1) g.bias = ls[l].gx[0].bias;
-      b.rows_out(g, b.mk(A_WS, ls[l].gxb.off + (int64_t)p * BT * 8 * H * 4), 8 * H);
-      ls[l].gx[p] = g; ls[l].cgx[p] = coef;
-      if (gx_merge) continue;
-      if (pipe && l == 1) pipe_gx1[p] = g; else b.push(F, OP_RUNGEMM, 200 + l).g = g;
+      ls[l].cgx[p] = coef;
+      for (int ck = 0; ck < nck; ++ck) {
+        const int d0 = ck * kMaxSeg;
+        RunGemm g = b.rows_gemm(lin, adt, rowlen, p * H, H, 8 * H, DT_F32);
+        if (l == 0) Builder::rows_slices(g, std::min(kMaxSeg, D - d0), Cl, d0 * Cl + p * (Cl / 2), Cl / 2);
+        const Builder::Coef cc = ck == 0 ? coef : Builder::Coef([=](int nn, int s, int j) -> int32_t { return coef(nn, s + d0, j); });
+        b.pack_weights(F, g, cc, nm + ".ih" + std::to_string(p) + (ck ? "_" + std::to_string(ck) : ""), 200 + l, p == 0 && ck == 0 ? &bias : nullptr);
+        if (p == 1 && ck == 0) g.bias = ls[l].gx[0].bias;
+        if (ck) g.flags |= kRunAccum;
+        b.rows_out(g, b.mk(A_WS, ls[l].gxb.off + (int64_t)p * BT * 8 * H * 4), 8 * H);
+        if (ck == 0) ls[l].gx[p] = g;
+        ls[l].gxc[p].push_back(g); ls[l].cgxc[p].push_back(cc);
+        if (gx_merge) continue;
+        if (pipe && l == 1) pipe_gx1[p] = g; else b.push(F, OP_RUNGEMM, 200 + l).g = g;
+      }
     }
-    if (gx_merge) {
+    for (int ck = 0; gx_merge && ck < nck; ++ck) {
       // both parts in ONE launch: the two GEMMs share their weights (W_ih of the real and the imag LSTM side by side) and differ only in the
       // input columns (part p) and the output slab - the part becomes the row index f of the run descriptor (rows (b, t, p))
-      RunGemm g = ls[l].gx[0];
+      RunGemm g = ls[l].gxc[0][ck];
       g.Fo = 2; g.M = (int)(2 * BT);
       g.fstride[0] = l == 0 ? Cl / 2 : H;
       g.y_fstride = (int)(BT * 8 * H);
@@ -700,11 +709,13 @@ Plan* build_dccrn_plan(const ModelConfig& cfg) {
       }
       auto dyp = [&](int p) { return b.mk(A_WS, dgates.off + (int64_t)p * dg_half); };      // dgates of part p
       b.cur_lane = lane_all ? 1 : 0;
-      for (int p = 0; p < 2; ++p) {
-        RunGemm fw = ls[l].gx[p];
-        fw.ydt = adt;                       // WGRAD reads dy = dgates (act dtype), not the fp32 gx the forward wrote
-        b.wgrad(R, fw, dyp(p), ls[l].cgx[p], 200 + l, &ls[l].bgx);
-      }
+      for (int p = 0; p < 2; ++p)
+        for (size_t ck = 0; ck < ls[l].gxc[p].size(); ++ck) {
+          RunGemm fw = ls[l].gxc[p][ck];
+          fw.ydt = adt;                     // WGRAD reads dy = dgates (act dtype), not the fp32 gx the forward wrote
+          fw.flags &= ~kRunAccum;
+          b.wgrad(R, fw, dyp(p), ls[l].cgxc[p][ck], 200 + l, ck == 0 ? &ls[l].bgx : nullptr);
+        }
       for (int g4 = 0; g4 < 4; ++g4) {       // W_hh: dW[n][k] = sum_t dgates[g][t][n] * h[g][t-1][k]
         const int p = g4 / 2, set = g4 % 2;
         RunGemm f = b.rows_gemm(b.mk(A_WS, ls[l].h.off + (int64_t)g4 * BT * H * esize(adt)), adt, H, 0, H, 4 * H, adt);

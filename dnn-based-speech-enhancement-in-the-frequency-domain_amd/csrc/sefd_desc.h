@@ -305,7 +305,8 @@ struct Ola {
   Ptr frames, wav, coff;
   Ptr dwav, dpad;              // backward: dpad [B][(T-1)*hop+win] = clampmask*dwav/(coff+1e-8) (0 in the trimmed borders)
   int32_t B, T, L, win, hop, trim;
-  int32_t noclamp, pad_;       // noclamp = 1: torch.istft semantics (no clamp_(-1, 1)); the ConviSTFT path of DCCRN / CRN clamps
+  int32_t noclamp, Lout;       // noclamp = 1: torch.istft semantics (no clamp_(-1, 1)); the ConviSTFT path of DCCRN / CRN clamps
+                               // Lout > 0: ConviSTFT returned only the first Lout < L samples (the hop does not tile the clip): the rest of wav is 0, its dwav unread
 };
 
 // est spec [B][T][NF+1][2] (fp32, slot layout above) <-> reference layout out_real/out_imag [B][NF][T] fp32

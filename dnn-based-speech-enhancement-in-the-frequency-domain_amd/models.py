@@ -126,6 +126,8 @@ class _Runtime:
         T, NF = p.T, p.NF
         self.wav = p.io(self.arenas, "wav", (B, L))
         self.out_wav = p.io(self.arenas, "out_wav", (B, L))
+        # ConviSTFT returns the samples the frames cover (tools_for_model.py:111): fewer than L when the hop does not tile the padded clip
+        self.Lout = min(L, (T - 1) * p.cfg.hop + p.cfg.win_len - 2 * (p.cfg.win_len - p.cfg.hop))
         self.out_real = p.io(self.arenas, "out_real", (B, NF, T))
         self.out_imag = p.io(self.arenas, "out_imag", (B, NF, T))
         self.g_wav = p.io(self.arenas, "grad_wav", (B, L))
@@ -147,7 +149,7 @@ class _DCCRNFunction(torch.autograd.Function):
         rt.stamp = getattr(rt, "stamp", 0) + 1     # the saved activations live in the runtime's arena, not in ctx
         ctx.owner, ctx.rt, ctx.stamp = owner, rt, rt.stamp
         ctx.n = len(params)
-        return rt.out_real.clone(), rt.out_imag.clone(), rt.out_wav.clone()
+        return rt.out_real.clone(), rt.out_imag.clone(), rt.out_wav[:, :rt.Lout].clone()
 
     @staticmethod
     def backward(ctx, g_real, g_imag, g_wav):
@@ -155,7 +157,8 @@ class _DCCRNFunction(torch.autograd.Function):
         if ctx.stamp != rt.stamp:
             raise RuntimeError("sefd: a later forward of the same (batch, length, mode) overwrote the activations this backward needs; "
                                "call backward before the next forward of that shape")
-        for dst, g in ((rt.g_real, g_real), (rt.g_imag, g_imag), (rt.g_wav, g_wav)):
+        rt.g_wav[:, rt.Lout:].zero_()                # samples behind the last frame are not part of the output
+        for dst, g in ((rt.g_real, g_real), (rt.g_imag, g_imag), (rt.g_wav[:, :rt.Lout], g_wav)):
             if g is None:
                 dst.zero_()
             else:
@@ -289,6 +292,9 @@ class _SefdModule(nn.Module):
         # data parallel: plans with two gradient buckets (decoder + LSTM complete before the encoder backward, see ddp.py)
         self._grad_buckets = 2 if (exchange is not None and exchange.active and not sync) else 1
         rt = self._runtime(B, L, inputs.device)
+        if rt.Lout != L:
+            raise ValueError(f"train_step: the frames of a {L}-sample clip cover {rt.Lout} samples (win_len {rt.plan.cfg.win_len}, win_inc {rt.plan.cfg.hop}); "
+                             "the losses compare the estimate with the target sample by sample - crop the clips to a length the hop tiles")
         rt.plan.tolerate_fault = exchange is not None and exchange.active       # a faulty rank keeps its collectives matched; all ranks raise at the guard check
         optimizer.bind(self)
         self._flat_nbt += 1

@@ -45,19 +45,19 @@ def synthesis_kernel(win_len=400, fft_len=512, win_type="hanning") -> np.ndarray
 
 
 def conv_stft(wav: torch.Tensor, win_len=400, hop=100, fft_len=512, win_type="hanning") -> torch.Tensor:
-    """[B, L] -> [B, 2*(N/2+1), T] (real rows then imag rows)."""
-    K = torch.from_numpy(analysis_kernel(win_len, fft_len, win_type=win_type).astype(np.float32))[:, None, :]
+    """[B, L] -> [B, 2*(N/2+1), T] (real rows then imag rows).  The bases take the input's dtype (float64: the oracle's own error is measured against it)."""
+    K = torch.from_numpy(analysis_kernel(win_len, fft_len, win_type=win_type)).to(wav.dtype)[:, None, :]     # float32 input: the reference's fp32 basis
     x = F.pad(wav[:, None, :], [win_len - hop, win_len - hop])
     return F.conv1d(x, K, stride=hop)
 
 
 def conv_istft(spec: torch.Tensor, win_len=400, hop=100, fft_len=512, win_type="hanning") -> torch.Tensor:
     """[B, 2*(N/2+1), T] -> [B, 1, L]."""
-    Kinv = torch.from_numpy(synthesis_kernel(win_len, fft_len, win_type).astype(np.float32))[:, None, :]
-    w = torch.from_numpy(window_of(win_len, win_type).astype(np.float32))[None, :, None]
+    Kinv = torch.from_numpy(synthesis_kernel(win_len, fft_len, win_type)).to(spec.dtype)[:, None, :]
+    w = torch.from_numpy(window_of(win_len, win_type)).to(spec.dtype)[None, :, None]
     out = F.conv_transpose1d(spec, Kinv, stride=hop)
     t = w.repeat(1, 1, spec.size(-1)) ** 2
-    coff = F.conv_transpose1d(t, torch.eye(win_len)[:, None, :], stride=hop)
+    coff = F.conv_transpose1d(t, torch.eye(win_len, dtype=spec.dtype)[:, None, :], stride=hop)
     out = out / (coff + 1e-8)
     return out[..., win_len - hop:-(win_len - hop)]
 

@@ -1131,6 +1131,7 @@ void run_op(const Op& op, const AB& ab) {
       for (int b = 0; b < d.B; ++b)
         for (int n = 0; n < d.L; ++n) {
           const int p = n + d.trim;
+          if (d.Lout > 0 && n >= d.Lout) { wav[(int64_t)b * d.L + n] = 0.f; continue; }      // behind the clip ConviSTFT returns
           double s = 0;
           for (int t = 0; t < d.T; ++t) { const int j = p - t * d.hop; if (j >= 0 && j < d.win) s += fr[((int64_t)b * d.T + t) * d.win + j]; }
           float v = (float)s / (coff[p] + 1e-8f);
@@ -1149,7 +1150,7 @@ void run_op(const Op& op, const AB& ab) {
         for (int p = 0; p < Lp; ++p) {
           float v = 0.f;
           const int s = p - d.trim;
-          if (s >= 0 && s < d.L) { const float w = wav[(int64_t)b * d.L + s]; if (w > -1.f && w < 1.f) v = dwav[(int64_t)b * d.L + s] / (coff[p] + 1e-8f); }
+          if (s >= 0 && s < (d.Lout > 0 ? d.Lout : d.L)) { const float w = wav[(int64_t)b * d.L + s]; if (w > -1.f && w < 1.f) v = dwav[(int64_t)b * d.L + s] / (coff[p] + 1e-8f); }
           dpad[(int64_t)b * Lp + p] = v;
         }
       break;
@@ -1222,6 +1223,17 @@ extern "C" int hostsim_enc0_accepts(const void* op_, int dy_off) {
   if (op.kind != OP_RUNGEMM && op.kind != OP_WGRAD) return -1;
   op.g.y_off += dy_off;
   return enc0_accepts(op.g, op.kind == OP_WGRAD) ? 1 : 0;
+}
+// test hook: the geometry of RUNGEMM / WGRAD descriptor `op_` that sefd_plan_op_info does not report:
+// out = {Npad, ldw, nseg, nsplit, ydt, n2, longest run, runs whose length is no multiple of 8}; -1: not such an op
+extern "C" int hostsim_gemm_fields(const void* op_, int64_t* out) {
+  const Op& op = *(const Op*)op_;
+  if (op.kind != OP_RUNGEMM && op.kind != OP_WGRAD) return -1;
+  const RunGemm& g = op.g;
+  int longest = 0, odd = 0;
+  for (int s = 0; s < g.nseg; ++s) { longest = std::max(longest, (int)g.seg[s].len); odd += g.seg[s].src >= 0 && g.seg[s].len % 8 != 0; }
+  out[0] = g.Npad; out[1] = g.ldw; out[2] = g.nseg; out[3] = g.nsplit; out[4] = g.ydt; out[5] = g.n2; out[6] = longest; out[7] = odd;
+  return 0;
 }
 // job order of the ticket-drawn recurrence launches (sefd_desc.h rows_pair_job / rows_bwd_job): out = {layer, chunk, block, tb, te}
 extern "C" void hostsim_rows_job(int bwd, int job, int nblk, int C, int T, int* out) {

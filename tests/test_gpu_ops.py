@@ -11,25 +11,10 @@ from oracle import losses as ol
 from oracle.dccrn import DCCRNConfig, dccrn_state_shapes
 from oracle.step import adam_update
 from oracle.weights import fill_state_dict_, formula_state_dict, test_signals as make_signals
+from plan_check import report_path
 from util import knobs, rel_err
 
 pytestmark = pytest.mark.gpu
-
-KIND = {1: "RUNGEMM", 2: "WGRAD", 3: "PACK", 4: "UNPACK", 5: "BN_FINALIZE", 6: "BN_APPLY", 7: "BN_BWD_REDUCE", 8: "BN_BWD_APPLY",
-        9: "LSTM_FWD", 10: "LSTM_BWD", 11: "COMBINE_FWD", 12: "COMBINE_BWD", 13: "MASK_FWD", 14: "MASK_BWD", 15: "OLA_FWD",
-        16: "OLA_BWD", 17: "SPECOUT_FWD", 18: "SPECOUT_BWD", 19: "MEMSET", 20: "SPLITSUM", 21: "BN_BWD_FINALIZE", 22: "MAGS", 23: "CELL_FWD", 24: "CELL_BWD", 25: "DROPOUT_FWD", 26: "DROPOUT_BWD", 27: "FSN_IN", 28: "FSN_SCALE", 29: "FSN_SBSUM",
-        30: "FSN_SBBUILD", 31: "FSN_OUT", 32: "FSN_OUT_BWD", 33: "FSN_SBBWD_SUM", 34: "FSN_SBBWD_APPLY", 35: "REFLECTPAD"}
-
-
-def _report_path(name):
-    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-    os.makedirs(d, exist_ok=True)
-    return os.path.join(d, name)
-
-
-def _typed(t_u8, dt):
-    return t_u8.view(torch.bfloat16 if dt == 1 else torch.float32)
-
 
 @pytest.mark.parametrize("model,B,L,mode,kn,ru,dtype", [("DCCRN", 3, 4000, "E", (16, 32, 32, 64, 64, 64), 128, "fp32"),
                                                         ("DCCRN", 1, 2400, "C", (32, 64, 128, 256, 256, 256), 256, "fp32"),
@@ -60,7 +45,8 @@ def test_every_op_against_host_simulator(model, B, L, mode, kn, ru, dtype):
     """Tolerances: fp32 buffers 1e-3 (observed <= 3e-6); bf16 buffers 1.6e-2 = two bf16 ulps of the largest element
     (simulator and kernel round slightly different fp32 accumulations of the SAME bf16 operands); fp32 state written by a whole
     bf16 recurrence op (LSTM_FWD / LSTM_BWD): 4e-3 = one bf16 ulp of h fed back through the frames."""
-    from simutil import PHASE_BWD, PHASE_FWD, Plan, fill_params, sim_run
+    from plan_check import ops_device_vs_sim
+    from simutil import Plan
     if L == 2401:                          # the wide-tile kernel needs M >= 4096 by default: lower the bar so that this small case runs it
         L = 2400
         knobs.set("CG256_MINM", "64")
@@ -105,107 +91,11 @@ def test_every_op_against_host_simulator(model, B, L, mode, kn, ru, dtype):
     knobs.unset("CG256_MINM")        # the plan is built: later tests get the default thresholds again
     knobs.unset("WG256_MINM")
     knobs.unset("LSTM_ROWS_MIN")
-    dev = plan.alloc_arenas("cuda")
-    host = plan.alloc_arenas("cpu")
-    fill_params(plan, dev, P)
-    torch.manual_seed(1)
-    if model == "FullSubNet":
-        plan.io(dev, "mag", (B, 257, L)).copy_(torch.rand(B, 257, L) * 3)
-        plan.io(dev, "grad_crm", (B, 257, L, 2)).copy_(torch.randn(B, 257, L, 2) * 1e-3)
-        plan.set_seed(dev, 77)
-    else:
-        x, y = make_signals(B, L)
-        plan.io(dev, "wav", (B, L)).copy_(x)
-        if model == "CRN":
-            plan.io(dev, "tgt", (B, L)).copy_(y)
-        plan.io(dev, "grad_wav", (B, L)).copy_(torch.randn(B, L) * 1e-3)
-        plan.io(dev, "grad_real", (B, plan.NF, plan.T)).copy_(torch.randn(B, plan.NF, plan.T) * 1e-4)
-        plan.io(dev, "grad_imag", (B, plan.NF, plan.T)).copy_(torch.randn(B, plan.NF, plan.T) * 1e-4)
-    # region table: (arena, byte offset, bytes, dtype, name); GRAD / STATE arenas are single fp32 regions
-    regions = []
-    for name in plan.buffer_names():
-        a, off, nb, dt = plan.buffer(name)
-        regions.append((a, off, nb, dt, name))
-    regions.append((2, 0, plan.arena_bytes[2], 0, "A_GRAD"))
-    regions.append((3, 0, plan.arena_bytes[3], 0, "A_STATE"))
-    check = [0, 2, 3, 5]
-    # The arenas stay on the device.  `host` mirrors the device state at every op boundary and `prev` is a second host copy
-    # of that state; after an op only the regions that the kernel or the simulator changed travel (device -> host), so the
-    # per-op cost is one device-side compare + one host-side memcmp instead of ten whole-arena copies.
-    for a in range(6):
-        host[a].copy_(dev[a])
-    prev = {a: host[a].clone() for a in check}
-    by_arena = {a: [r for r in regions if r[0] == a and r[2] > 0] for a in check}
-    # 8-byte words: every region starts on a 256-byte boundary, so a word never straddles two regions
-    w64 = {a: (dev[a].view(torch.uint8).numel() // 8) for a in check}
-    lo_idx = {a: torch.tensor([r[1] // 8 for r in by_arena[a]], device="cuda") for a in check}
-    hi_idx = {a: torch.tensor([min((r[1] + r[2] + 7) // 8, w64[a]) for r in by_arena[a]], device="cuda") for a in check}
-    # host side: which regions did the SIMULATOR change?  One vectorised pass per arena (words -> 256-byte blocks -> prefix sums; regions start on
-    # 256-byte boundaries, so a block never straddles two regions) instead of one memcmp per region and op (28 000 torch.equal calls per case: half of the
-    # suite's run time through round 5)
-    nblk = {a: (w64[a] + 31) // 32 for a in check}
-    lo_blk = {a: torch.tensor([r[1] // 256 for r in by_arena[a]]) for a in check}
-    hi_blk = {a: torch.tensor([min((r[1] + r[2] + 255) // 256, nblk[a]) for r in by_arena[a]]) for a in check}
-
-    def host_changed(a):
-        h64 = host[a].view(torch.uint8)[:w64[a] * 8].view(torch.int64)
-        p64 = prev[a].view(torch.uint8)[:w64[a] * 8].view(torch.int64)
-        ne = h64 != p64
-        if ne.numel() % 32:
-            ne = torch.cat([ne, torch.zeros(32 - ne.numel() % 32, dtype=torch.bool)])
-        cs = torch.cat([torch.zeros(1, dtype=torch.int64), ne.view(-1, 32).any(1).to(torch.int64).cumsum(0)])
-        return ((cs[hi_blk[a]] - cs[lo_blk[a]]) > 0).tolist()
-    lines, bad = [], []
-    for phase in (PHASE_FWD, PHASE_BWD):
-        kinds, tags = plan.op_kinds(phase)
-        for i in range(plan.num_ops(phase)):
-            dbefore = {a: dev[a].view(torch.uint8)[:w64[a] * 8].view(torch.int64).clone() for a in check}
-            sim_run(plan, phase, host, i, i + 1)
-            plan.run(phase, dev, 0, i, i + 1)
-            worst, nchg, stray, where = 0.0, 0, 0, ""
-            for a in check:
-                if not by_arena[a]:
-                    continue
-                d64 = dev[a].view(torch.uint8)[:w64[a] * 8].view(torch.int64)
-                cs = torch.cumsum(torch.cat([torch.zeros(1, dtype=torch.int32, device="cuda"), (d64 != dbefore[a]).to(torch.int32)]), 0)
-                dflags = ((cs[hi_idx[a]] - cs[lo_idx[a]]) > 0).cpu().tolist()        # the one synchronising read per arena
-                hflags = host_changed(a)
-                h8, p8, d8 = host[a].view(torch.uint8), prev[a].view(torch.uint8), dev[a].view(torch.uint8)
-                for (ra, off, nb, dt, name), dchg, hchg in zip(by_arena[a], dflags, hflags):
-                    if not (hchg or dchg):
-                        continue
-                    g8 = d8[off:off + nb].cpu() if dchg else p8[off:off + nb]
-                    if hchg:
-                        hv, gv = _typed(h8[off:off + nb], dt).double(), _typed(g8, dt).double()
-                        den = float(hv.abs().max())
-                        err = float((hv - gv).abs().max()) / (den if den > 0 else 1.0)
-                        if not np.isfinite(err):
-                            err = float("inf")
-                        tol = 1.6e-2 if dt == 1 else 1e-3
-                        if dt != 1 and dtype == "bf16" and int(kinds[i]) == 1 and name.endswith(".bnpart"):
-                            tol = 4e-3     # fp32 partial sums of the bf16 gradient tile this launch ALSO stores: where kernel and simulator round an
-                                           # element of that tile to different bf16 neighbours (allowed above: 2 ulps), a 128-row sum with cancellation
-                                           # moves by up to that ulp (seen 1.06e-3 of the region's largest sum)
-                        if dt != 1 and dtype == "bf16" and int(kinds[i]) in (9, 10):
-                            tol = 4e-3     # fp32 state of a bf16 recurrence (cell state, dh): h_t is rounded to bf16 every frame, and a
-                                           # rounding flip (one bf16 ulp = 4e-3 of h) between kernel and simulator feeds back into c
-                        nchg += hv.numel()
-                        if err / tol > worst:
-                            worst, where = err / tol, f"{name} err {err:.2e} tol {tol:.0e}"
-                    else:
-                        # stray write: the kernel changed bytes of a region the simulator did not touch
-                        stray += int((g8 != p8[off:off + nb]).sum())
-                    h8[off:off + nb].copy_(g8)                                        # both host copies := device state
-                    if dchg:
-                        p8[off:off + nb].copy_(g8)
-            lines.append(f"phase {phase} op {i:3d} {KIND.get(int(kinds[i]), str(int(kinds[i]))):16s} tag {int(tags[i]):4d} elems {nchg:9d} "
-                         f"err/tol {worst:.3e} stray {stray} {where}")
-            if not (worst < 1.0) or stray:
-                bad.append(lines[-1])
+    lines, bad = ops_device_vs_sim(plan, P, model, B, L, dtype)
     knobs.unset("LSTM_MT")
     knobs.unset("LSTM_RPW")
     knobs.unset("DIRECT_MINM")
-    with open(_report_path(f"ops_report_{model}_B{B}_{mode.replace('/', '-')}_{dtype}_{L}.txt"), "w") as f:
+    with open(report_path(f"ops_report_{model}_B{B}_{mode.replace('/', '-')}_{dtype}_{L}.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
     assert not bad, "\n".join(bad[:20])
 
@@ -383,5 +273,5 @@ def _syncbn_ranks_on_one_gpu(dtype, kn, world, knob):
     # layer's gradient by 0.3 .. 0.9
     errs = check_syncbn_result(res, dtype, only=DEFAULT_KN_ONLY if kn == DEFAULT_KN and dtype == "bf16" else None, grad_bar=5e-2 if dtype == "bf16" else None)
     worst = sorted(errs.items(), key=lambda kv: -kv[1])[:8]
-    with open(_report_path(f"syncbn_{dtype}_kn{kn[0]}_w{world}_{knob[0] if knob else 'default'}.txt"), "w") as f:
+    with open(report_path(f"syncbn_{dtype}_kn{kn[0]}_w{world}_{knob[0] if knob else 'default'}.txt"), "w") as f:
         f.write("\n".join(f"{k} {v:.3e}" for k, v in worst) + "\n")
