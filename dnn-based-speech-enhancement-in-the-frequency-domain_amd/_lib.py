@@ -66,8 +66,8 @@ def lib():
         "sefd_loss_rows_ws_floats": (i64, [i64]),
         "sefd_loss_rows_forward": (i32, [i32, vp, vp, i64, i32, vp, vp, vp]),
         "sefd_loss_rows_backward": (i32, [i32, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
-        "sefd_lms_forward": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, C.POINTER(i32), i32, i32, vp, vp, vp]),
-        "sefd_lms_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, C.POINTER(i32), i32, i32, vp, vp, vp, vp]),
+        "sefd_lms_forward": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, C.POINTER(i32), i32, i32, vp, vp, vp]),
+        "sefd_lms_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, C.POINTER(i32), i32, i32, vp, vp, vp, vp]),
         "sefd_fsn_targets": (i32, [vp, vp, i64, vp, vp, vp, vp]),
         "sefd_mix_snr": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "sefd_composite_ws_bytes": (i64, [i32, i32, i32]),

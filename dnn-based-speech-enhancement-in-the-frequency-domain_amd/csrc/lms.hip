@@ -94,8 +94,10 @@ __global__ void lms_reduce_kernel(const float* rowloss, int64_t n, float* out) {
 }
 
 int fill(LmsArgs& a, const float* cr, const float* ci, const float* er, const float* ei, int B, int NF, int T, const int32_t* bands,
-         const float* weights, int nbands, const int32_t* scale_sizes, int nscales, int nfft) {
-  if (NF > kMaxNF || nbands > kMaxBands || nscales > kMaxScales || (NF * T) % NF != 0) return -1;
+         const float* weights, int nbands, int band_bins, const int32_t* scale_sizes, int nscales, int nfft) {
+  if (B <= 0 || NF <= 0 || T <= 0 || nfft <= 0 || NF > kMaxNF || nbands <= 0 || nbands > kMaxBands || nscales <= 0 || nscales > kMaxScales) return -1;
+  // the band rows live on the device; their extent (largest first bin + taps, from the host that built them) must lie within the NF staged bins
+  if (band_bins < 0 || band_bins > NF) return -1;
   a.cr = cr; a.ci = ci; a.er = er; a.ei = ei; a.bands = bands; a.weights = weights;
   a.B = B; a.NF = NF; a.T = T; a.nbands = nbands; a.nscales = nscales; a.nfft = nfft;
   for (int s = 0; s < nscales; ++s) a.nb[s] = scale_sizes[s];
@@ -105,10 +107,10 @@ int fill(LmsArgs& a, const float* cr, const float* ci, const float* er, const fl
 
 extern "C" {
 int32_t sefd_lms_forward(const float* clean_r, const float* clean_i, const float* est_r, const float* est_i, int32_t B, int32_t NF, int32_t T,
-                         const int32_t* bands, const float* weights, int32_t nbands, const int32_t* scale_sizes_host, int32_t nscales,
-                         int32_t nfft, float* rowloss_ws, float* loss_out, void* stream) {
+                         const int32_t* bands, const float* weights, int32_t nbands, int32_t band_bins, const int32_t* scale_sizes_host,
+                         int32_t nscales, int32_t nfft, float* rowloss_ws, float* loss_out, void* stream) {
   LmsArgs a{};
-  if (fill(a, clean_r, clean_i, est_r, est_i, B, NF, T, bands, weights, nbands, scale_sizes_host, nscales, nfft)) return -1;
+  if (fill(a, clean_r, clean_i, est_r, est_i, B, NF, T, bands, weights, nbands, band_bins, scale_sizes_host, nscales, nfft)) return -1;
   a.rowloss = rowloss_ws;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL((lms_kernel<false>), dim3(T, B), dim3(128), 0, st, a);
@@ -116,10 +118,10 @@ int32_t sefd_lms_forward(const float* clean_r, const float* clean_i, const float
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 int32_t sefd_lms_backward(const float* clean_r, const float* clean_i, const float* est_r, const float* est_i, int32_t B, int32_t NF, int32_t T,
-                          const int32_t* bands, const float* weights, int32_t nbands, const int32_t* scale_sizes_host, int32_t nscales,
-                          int32_t nfft, const float* grad_scale, float* grad_est_r, float* grad_est_i, void* stream) {
+                          const int32_t* bands, const float* weights, int32_t nbands, int32_t band_bins, const int32_t* scale_sizes_host,
+                          int32_t nscales, int32_t nfft, const float* grad_scale, float* grad_est_r, float* grad_est_i, void* stream) {
   LmsArgs a{};
-  if (fill(a, clean_r, clean_i, est_r, est_i, B, NF, T, bands, weights, nbands, scale_sizes_host, nscales, nfft)) return -1;
+  if (fill(a, clean_r, clean_i, est_r, est_i, B, NF, T, bands, weights, nbands, band_bins, scale_sizes_host, nscales, nfft)) return -1;
   a.gscale = grad_scale; a.ger = grad_est_r; a.gei = grad_est_i;
   hipLaunchKernelGGL((lms_kernel<true>), dim3(T, B), dim3(128), 0, reinterpret_cast<hipStream_t>(stream), a);
   return hipGetLastError() == hipSuccess ? 0 : -2;

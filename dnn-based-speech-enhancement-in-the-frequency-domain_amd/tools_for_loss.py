@@ -206,13 +206,17 @@ _BANK_CACHE = {}
 
 
 def _banks(device, nfft):
-    """(band rows, tap weights, number of bands, bands per scale) of the three mel banks on `device`."""
+    """(band rows, tap weights, number of bands, bands per scale, extent) of the three mel banks on `device`.  The extent is the largest
+    first bin + taps over the rows: the kernels stage NF bins per row of the input, and the entry points refuse a table that reaches past them."""
     key = (str(device), nfft)
     if key not in _BANK_CACHE:
         bands, weights = _band_table(nfft)
+        extent = max(r[0] + r[1] for r in bands)
+        if extent > int(nfft / 2) + 1 or any(r[0] < 0 or r[1] < 0 or r[2] + r[1] > len(weights) for r in bands):
+            raise ValueError(f"mel band table of fft_len {nfft} reaches past its {int(nfft / 2) + 1} bins or its {len(weights)} taps")
         _BANK_CACHE[key] = (torch.tensor(bands, dtype=torch.int32, device=device).contiguous(),
                             torch.tensor(weights or [0.0], dtype=torch.float32, device=device), len(bands),
-                            (C.c_int32 * len(MEL_SCALES))(*MEL_SCALES))
+                            (C.c_int32 * len(MEL_SCALES))(*MEL_SCALES), extent)
     return _BANK_CACHE[key]
 
 
@@ -226,12 +230,14 @@ class _LMS(torch.autograd.Function):
         clean_r, clean_i, er, ei = f(clean_r), f(clean_i), f(est_r), f(est_i)
         B, NF, T = er.shape
         nfft = cfg.fft_len
-        bands, weights, nbands, sizes = _banks(er.device, nfft)
+        if NF != int(nfft / 2) + 1:
+            raise ValueError(f"LMS takes [B, {int(nfft / 2) + 1}, T] arrays at cfg.fft_len = {nfft} (the mel banks are built for that many bins): got {NF}")
+        bands, weights, nbands, sizes, extent = _banks(er.device, nfft)
         ws = torch.empty(B * T, dtype=torch.float32, device=er.device)
         out = torch.empty((), dtype=torch.float32, device=er.device)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = L_.sefd_lms_forward(_vp(clean_r), _vp(clean_i), _vp(er), _vp(ei), B, NF, T, _vp(bands), _vp(weights), nbands, sizes,
-                                 len(MEL_SCALES), nfft, _vp(ws), _vp(out), stream)
+        rc = L_.sefd_lms_forward(_vp(clean_r), _vp(clean_i), _vp(er), _vp(ei), B, NF, T, _vp(bands), _vp(weights), nbands, extent,
+                                 sizes, len(MEL_SCALES), nfft, _vp(ws), _vp(out), stream)
         if rc != 0:
             raise RuntimeError(f"sefd_lms_forward failed ({rc})")
         ctx.t = (clean_r, clean_i, er, ei)
@@ -242,12 +248,12 @@ class _LMS(torch.autograd.Function):
         L_ = _lib.lib()
         clean_r, clean_i, er, ei = ctx.t
         B, NF, T = er.shape
-        bands, weights, nbands, sizes = _banks(er.device, cfg.fft_len)
+        bands, weights, nbands, sizes, extent = _banks(er.device, cfg.fft_len)
         gr = torch.empty_like(er)
         gi = torch.empty_like(er) if ei is not None else None
         gs = g.float().contiguous().view(1)
-        rc = L_.sefd_lms_backward(_vp(clean_r), _vp(clean_i), _vp(er), _vp(ei), B, NF, T, _vp(bands), _vp(weights), nbands, sizes,
-                                  len(MEL_SCALES), cfg.fft_len, _vp(gs), _vp(gr), _vp(gi), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = L_.sefd_lms_backward(_vp(clean_r), _vp(clean_i), _vp(er), _vp(ei), B, NF, T, _vp(bands), _vp(weights), nbands, extent,
+                                  sizes, len(MEL_SCALES), cfg.fft_len, _vp(gs), _vp(gr), _vp(gi), C.c_void_p(torch.cuda.current_stream().cuda_stream))
         if rc != 0:
             raise RuntimeError(f"sefd_lms_backward failed ({rc})")
         return None, None, gr, gi

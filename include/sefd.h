@@ -149,13 +149,14 @@ int32_t sefd_loss_dp_finish(int32_t rows, int64_t n, float* ws, int32_t world, f
  * clean_* / est_*: fp32 [B][NF][T] device (reference layout).  If the *_i pointers are NULL the *_r arrays are magnitudes
  * already (get_array_lms_loss(clean_mags, est_mags) signature); otherwise mag = sqrt(r^2 + i^2 + 1e-7) is fused in.
  * bands: int32 [nbands][4] = {first bin, taps, weight offset, scale index}; weights: the triangle taps (melFilterBank);
+ * band_bins: the largest first bin + taps over the band rows, from the host that built them - a table that reaches past NF is refused (-1);
  * scale_sizes_host: HOST int32[nscales] = filters per scale (16, 32, 64).  rowloss_ws: fp32 [B*T] device scratch. */
 int32_t sefd_lms_forward(const float* clean_r, const float* clean_i, const float* est_r, const float* est_i, int32_t B, int32_t NF, int32_t T,
-                         const int32_t* bands, const float* weights, int32_t nbands, const int32_t* scale_sizes_host, int32_t nscales,
-                         int32_t nfft, float* rowloss_ws, float* loss_out, void* stream);
+                         const int32_t* bands, const float* weights, int32_t nbands, int32_t band_bins, const int32_t* scale_sizes_host,
+                         int32_t nscales, int32_t nfft, float* rowloss_ws, float* loss_out, void* stream);
 int32_t sefd_lms_backward(const float* clean_r, const float* clean_i, const float* est_r, const float* est_i, int32_t B, int32_t NF, int32_t T,
-                          const int32_t* bands, const float* weights, int32_t nbands, const int32_t* scale_sizes_host, int32_t nscales,
-                          int32_t nfft, const float* grad_scale, float* grad_est_r, float* grad_est_i, void* stream);
+                          const int32_t* bands, const float* weights, int32_t nbands, int32_t band_bins, const int32_t* scale_sizes_host,
+                          int32_t nscales, int32_t nfft, const float* grad_scale, float* grad_est_r, float* grad_est_i, void* stream);
 
 /* ---- PMSQE perceptual loss (call chain tools_for_loss.py:253-269 `get_array_pmsqe_loss`, models.py:313-314) ----------------------
  * The arithmetic is third-party (asteroid SingleSrcPMSQE + PITLossWrapper('pw_pt') + asteroid_filterbanks STFTFB / Encoder / mag), absent

@@ -107,7 +107,7 @@ def lms_loss(clean_mags: torch.Tensor, est_mags: torch.Tensor, scales=(16, 32, 6
     for b in range(B):
         per = 0.0
         for nb in scales:
-            bank = torch.from_numpy(mel_filter_bank(nb, n_fft))
+            bank = torch.from_numpy(mel_filter_bank(nb, n_fft)).to(clean_mags.dtype)      # float32 triangles, exact in either dtype
             outs = []
             for x in (clean_mags[b], est_mags[b]):
                 p = x.contiguous().view(-1, n_fft // 2 + 1) / n_fft        # Q8: NOT transposed

@@ -14,7 +14,12 @@ function based on the perceptual evaluation of the speech quality", IEEE SPL 201
   PIT: minimum over the permutations of the seconds of the mean pair loss, then mean over the batch           (PITLossWrapper 'pw_pt')
 
 torch float64 on the CPU; autograd of this restatement is the gradient oracle of tests/test_gpu_pmsqe.py.  The tables are the data module
-pmsqe_tables.py of the package (constants of ITU-T P.862.2), loaded by path - no product code runs here."""
+pmsqe_tables.py of the package (constants of ITU-T P.862.2), loaded by path - no product code runs here.
+
+The formulas follow the dtype of their input (float64 by default; float32 measures what the number format alone costs, the "reference alone"
+figure of tests/test_perceptual_cases_cpu.py).  Two test-only extras ride on the same formulas: `census=True` counts which branch every
+element / frame takes (CENSUS_ARMS), and `mutant=` (MUTANTS) evaluates the same VALUE with ONE gradient arm changed the way a kernel bug
+would change it - the sensitivity check of the case table, never a reference."""
 import importlib.util
 import itertools
 import math
@@ -33,7 +38,7 @@ FS, NFFT, HOP, NB, NBINS = 16000, 512, 256, 49, 257
 ALPHA, BETA, EPS = 0.1, 0.309 * 0.1, 1e-8
 
 
-def constants():
+def constants(dtype=torch.float64):
     thr = torch.tensor(T_.ABS_THRESH_POWER, dtype=torch.float64)
     cb = np.array(T_.CENTRE_OF_BAND_BARK)
     h = np.where(cb >= 4, 1.0, 6.0 / (cb + 2.0))
@@ -49,78 +54,148 @@ def constants():
     mask[12:104] = 1.0
     mask[104] = 0.5
     mask = mask * (2.0 * (NFFT + 2.0) / NFFT ** 2)                           # sqrt-Hann power correction factor 2.0
-    return thr, zp, width, M, mask
+    return tuple(t.to(dtype) for t in (thr, zp, width, M, mask))
 
 
-def stft_filters():
+def stft_filters(dtype=torch.float64):
     n = np.arange(NFFT)
     win = np.hanning(NFFT + 1)[:-1] ** 0.5
     ang = 2 * np.pi * np.outer(np.arange(NBINS), n) / NFFT
     scale = 0.5 * math.sqrt(NFFT * NFFT / HOP)
-    return torch.tensor(np.cos(ang) * win / scale), torch.tensor(-np.sin(ang) * win / scale)     # [257, 512] each
+    return torch.tensor(np.cos(ang) * win / scale).to(dtype), torch.tensor(-np.sin(ang) * win / scale).to(dtype)     # [257, 512] each
 
 
 def spectra(wav, power=False):
-    """wav [N, L] float64 -> [N, S, T, 257] (S seconds, T = 61 frames per second)."""
+    """wav [N, L] float64 or float32 -> [N, S, T, 257] of the same dtype (S seconds, T = 61 frames per second)."""
     N, L = wav.shape
     if L % FS:
         raise ValueError("view(N, -1, fs) needs whole seconds (tools_for_loss.py:262)")
     seg = wav.reshape(N, L // FS, FS)
     fr = seg.unfold(-1, NFFT, HOP)                                            # [N, S, T, 512]
-    C, S = stft_filters()
+    C, S = stft_filters(wav.dtype)
     re, im = fr @ C.T, fr @ S.T
     p = re * re + im * im
     return p if power else torch.sqrt(p + 1e-8)
 
 
-def single_src_pmsqe(deg, ref):
-    """deg, ref: [..., T, 257] spectra -> [...] loss."""
-    thr, zp, width, M, mask = constants()
+# every branch of the loss that has its own arm in a hand-derived gradient: (arm, what is counted)
+CENSUS_ARMS = ("eq_below", "eq_free", "eq_above",                    # Bark equaliser ratio < 0.01 / inside / > 100, per (pair, band)
+               "gain_below", "gain_free", "gain_above",              # gain ratio < 3e-4 / inside / > 5, per frame
+               "frame_silent", "frame_active",                       # the reference frame counts for the equaliser or not
+               "deg_below_thr", "deg_above_thr",                     # equalised degraded band under / at or over the hearing threshold
+               "diff_nonpos", "diff_pos_ld_gt_lr", "diff_pos_ld_lt_lr",   # |ld - lr| - 0.25 min(lr, ld) <= 0, or > 0 with either sign of ld - lr
+               "asym_below3", "asym_3_to_12", "asym_at12",           # asymmetry factor zeroed / free / saturated
+               "d_under_cap", "d_at_cap", "da_under_cap", "da_at_cap")    # d_frame / w and da_frame / w against the cap of 45
+
+# one gradient arm changed each, the value untouched (straight-through: x + (f(x) - x).detach() has f's value and x's gradient)
+MUTANTS = ("eq_clamp_passes", "gain_clamp_passes", "d_cap_passes", "da_cap_passes", "asym_passes_at12", "asym_passes_below3",
+           "min_term_dropped", "loudness_ungated", "gm_dropped", "eq_ppb_deg_dropped")
+
+
+def _through(x, fx):
+    """Value of fx, gradient of x."""
+    return x + (fx - x).detach()
+
+
+def single_src_pmsqe(deg, ref, census=False, mutant=None):
+    """deg, ref: [..., T, 257] spectra -> [...] loss; with census=True -> (loss, {arm of CENSUS_ARMS: members})."""
+    if mutant is not None and mutant not in MUTANTS:
+        raise ValueError(mutant)
+    mu = lambda name: mutant == name
+    thr, zp, width, M, mask = constants(deg.dtype)
     Tn = deg.shape[-2]
 
-    def sll(x):
+    def sll(x, cut=False):
         mean_pow = (x * mask).mean(-1, keepdim=True).sum(-2, keepdim=True) / Tn
-        return 1e7 * x / mean_pow
+        return 1e7 * x / (mean_pow.detach() if cut else mean_pow)
 
     bark = lambda x: T_.SP_16K * (x @ M)
     audible = lambda b, f: torch.where(b > thr * f, b, torch.zeros_like(b)).sum(-1, keepdim=True)
-    rb, db = bark(sll(ref)), bark(sll(deg))
+    rb, db = bark(sll(ref)), bark(sll(deg, mu("gm_dropped")))
     # Bark frequency equalisation of the degraded spectrum
     not_silent = audible(rb, 100.0) >= 1e7
     cond = rb >= thr * 100.0
     z = torch.zeros_like(rb)
     ppb_ref = torch.where(not_silent, torch.where(cond, rb, z), z).sum(-2, keepdim=True)
     ppb_deg = torch.where(not_silent, torch.where(cond, db, z), z).sum(-2, keepdim=True)
-    db = torch.clamp((ppb_ref + 1000.0) / (ppb_deg + 1000.0), 0.01, 100.0) * db
+    if mu("eq_ppb_deg_dropped"):
+        ppb_deg = ppb_deg.detach()
+    eq_raw = (ppb_ref + 1000.0) / (ppb_deg + 1000.0)
+    eq = torch.clamp(eq_raw, 0.01, 100.0)
+    db = (_through(eq_raw, eq) if mu("eq_clamp_passes") else eq) * db
     # gain equalisation
-    db = torch.clamp((audible(rb, 1.0) + 5e3) / (audible(db, 1.0) + 5e3), 3e-4, 5.0) * db
+    gain_raw = (audible(rb, 1.0) + 5e3) / (audible(db, 1.0) + 5e3)
+    gain = torch.clamp(gain_raw, 3e-4, 5.0)
+    db = (_through(gain_raw, gain) if mu("gain_clamp_passes") else gain) * db
 
-    def loudness(b):
+    def loudness(b, ungated=False):
         a = (thr / 0.5) ** zp
         l = T_.SL_16K * a * ((0.5 + 0.5 * b / thr) ** zp - 1.0)
-        return torch.where(b < thr, torch.zeros_like(b), l)
+        gated = torch.where(b < thr, torch.zeros_like(b), l)
+        return _through(l, gated) if ungated else gated
 
-    lr, ld = loudness(rb), loudness(db)
-    sym = torch.clamp((ld - lr).abs() - 0.25 * torch.minimum(lr, ld), min=0.0)
+    lr, ld = loudness(rb), loudness(db, mu("loudness_ungated"))
+    mn = torch.minimum(lr, ld)
+    diff = (ld - lr).abs() - 0.25 * (mn.detach() if mu("min_term_dropped") else mn)
+    sym = torch.clamp(diff, min=0.0)
     asym = ((db + 50.0) / (rb + 50.0)) ** 1.2
-    asym_d = torch.where(asym < 3.0, torch.zeros_like(asym), torch.clamp(asym, max=12.0)) * sym
+    asym_f = torch.where(asym < 3.0, torch.zeros_like(asym), torch.clamp(asym, max=12.0))
+    if mu("asym_passes_at12"):
+        asym_f = torch.where(asym >= 12.0, _through(asym, asym_f), asym_f)
+    if mu("asym_passes_below3"):
+        asym_f = torch.where(asym < 3.0, _through(asym, asym_f), asym_f)
+    asym_d = asym_f * sym
     d_frame = torch.sqrt(((sym * width) ** 2 + EPS).sum(-1, keepdim=True)) * math.sqrt(float(width.sum()))
     da_frame = (asym_d * width).sum(-1, keepdim=True)
     w = ((audible(rb, 1.0) + 1e5) / 1e7) ** 0.04
     wd, wda = torch.clamp(d_frame / w, max=45.0), torch.clamp(da_frame / w, max=45.0)
-    return (ALPHA * wd + BETA * wda).sum((-1, -2)) / Tn
+    if mu("d_cap_passes"):
+        wd = _through(d_frame / w, wd)
+    if mu("da_cap_passes"):
+        wda = _through(da_frame / w, wda)
+    loss = (ALPHA * wd + BETA * wda).sum((-1, -2)) / Tn
+    if not census:
+        return loss
+    n = lambda m: int(m.sum())
+    pos = diff > 0
+    counts = {"eq_below": n(eq_raw < 0.01), "eq_free": n((eq_raw >= 0.01) & (eq_raw <= 100.0)), "eq_above": n(eq_raw > 100.0),
+              "gain_below": n(gain_raw < 3e-4), "gain_free": n((gain_raw >= 3e-4) & (gain_raw <= 5.0)), "gain_above": n(gain_raw > 5.0),
+              "frame_silent": n(~not_silent), "frame_active": n(not_silent),
+              "deg_below_thr": n(db < thr), "deg_above_thr": n(db >= thr),
+              "diff_nonpos": n(~pos), "diff_pos_ld_gt_lr": n(pos & (ld > lr)), "diff_pos_ld_lt_lr": n(pos & (ld < lr)),
+              "asym_below3": n(asym < 3.0), "asym_3_to_12": n((asym >= 3.0) & (asym < 12.0)), "asym_at12": n(asym >= 12.0),
+              "d_under_cap": n(d_frame / w < 45.0), "d_at_cap": n(d_frame / w >= 45.0),
+              "da_under_cap": n(da_frame / w < 45.0), "da_at_cap": n(da_frame / w >= 45.0)}
+    assert tuple(counts) == CENSUS_ARMS
+    return loss, counts
 
 
-def pairwise(est_wav, clean_wav, power=False):
+def pairwise(est_wav, clean_wav, power=False, mutant=None):
     """[N, S, S]: loss of estimate second i against clean second j."""
     e, c = spectra(est_wav, power), spectra(clean_wav, power)
-    return single_src_pmsqe(e[:, :, None], c[:, None, :])
+    return single_src_pmsqe(e[:, :, None], c[:, None, :], mutant=mutant)
 
 
-def pmsqe_loss(clean_wav, est_wav, power=False):
-    """get_array_pmsqe_loss(clean_array, est_array) (tools_for_loss.py:258-269) -> scalar."""
-    pw = pairwise(est_wav.double(), clean_wav.double(), power)
+def pmsqe_loss(clean_wav, est_wav, power=False, dtype=torch.float64, mutant=None, details=False):
+    """get_array_pmsqe_loss(clean_array, est_array) (tools_for_loss.py:258-269) -> scalar, evaluated in `dtype`.
+
+    details=True -> (loss, info): info["perm"] [N, S] the clean second each estimate second is paired with, info["gap"] [N] the relative gap
+    between the best and the second-best permutation mean (inf with one second), info["census"] the branch census of the chosen pairs - the
+    ones the gradient runs through."""
+    est_wav, clean_wav = est_wav.to(dtype), clean_wav.to(dtype)
+    pw = pairwise(est_wav, clean_wav, power, mutant)
     S = pw.shape[1]
     perms = list(itertools.permutations(range(S)))
     per = torch.stack([sum(pw[:, i, p[i]] for i in range(S)) / S for p in perms], 1)       # [N, S!]
-    return per.min(1).values.mean()
+    loss = per.min(1).values.mean()
+    if not details:
+        return loss
+    with torch.no_grad():
+        order = per.sort(1)
+        perm = torch.tensor(perms)[order.indices[:, 0]]                                     # [N, S]
+        best = order.values[:, 0]
+        gap = (order.values[:, 1] - best) / best if len(perms) > 1 else torch.full_like(best, float("inf"))
+        e, c = spectra(est_wav, power), spectra(clean_wav, power)
+        c = torch.gather(c, 1, perm[:, :, None, None].expand(-1, -1, c.shape[2], c.shape[3]))
+        _, counts = single_src_pmsqe(e, c, census=True)
+    return loss, {"perm": perm, "gap": gap, "census": counts}
