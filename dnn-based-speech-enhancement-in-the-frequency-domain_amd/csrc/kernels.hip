@@ -734,7 +734,9 @@ __global__ void ola_fwd_kernel(const Ola d, const ArenaBases ab) {
     int t0 = (p - d.win + d.hop) / d.hop; if (p - d.win + 1 <= 0) t0 = 0;
     float s = 0.f;
     for (int t = t0; t <= t1; ++t) s += fr[((int64_t)b * d.T + t) * d.win + (p - t * d.hop)];
-    s = s / (coff[p] + 1e-8f);
+    // noclamp = the torch.istft plan: torch divides by the envelope alone (its planner refuses a clip that reaches an envelope of zero);
+    // the 1e-8 is ConviSTFT's (DCCRN / CRN), and at the last samples of a clip it is as large as the envelope itself
+    s = d.noclamp ? s / coff[p] : s / (coff[p] + 1e-8f);
     wav[i] = d.noclamp ? s : fminf(1.f, fmaxf(-1.f, s));
   }
 }

@@ -39,11 +39,24 @@ Plan* build_torchstft_plan(const ModelConfig& cfg) {
   b.c = cfg;
   const int B = cfg.B, L = cfg.L, W = cfg.win_len, hop = cfg.hop, NFFT = cfg.fft_len;
   const int pad = NFFT / 2, Lp = L + 2 * pad;
-  const int T = 1 + L / hop;
   const int NF = NFFT / 2 + 1, NS = NF + 1, SW = NS * 2;
-  P->T = T;
   P->NF = NF;
-  if (hop % 4 != 0 || pad >= L) { P->error = "torch.stft plan: hop must be a multiple of 4 and the clip longer than fft_len/2"; return P; }
+  // one sentence per limit: the message names the one that was hit
+  if (hop <= 0 || hop % 4 != 0) {
+    P->error = "torch.stft plan: hop " + std::to_string(hop) + " is not a positive multiple of 4 (a limit of this planner's frame GEMM, whose rows start "
+               "hop samples apart; torch.stft has no such limit)";
+    return P;
+  }
+  if (W <= 0 || W > NFFT) {                                   // win[left + j] below would be written in front of the table
+    P->error = "torch.stft plan: win_len " + std::to_string(W) + " must lie in 1 .. fft_len = " + std::to_string(NFFT);
+    return P;
+  }
+  if (pad >= L) {
+    P->error = "torch.stft plan: a clip of " + std::to_string(L) + " samples is not longer than fft_len/2 = " + std::to_string(pad) + ", which reflect padding needs";
+    return P;
+  }
+  const int T = 1 + L / hop;
+  P->T = T;
   Ptr io_wav = b.io("wav", (int64_t)B * L);
   Ptr io_spec = b.io("spec", (int64_t)B * NF * T * 2);
   Ptr wpad = b.ws("wpad", (int64_t)B * Lp, DT_F32);
@@ -56,20 +69,28 @@ Plan* build_torchstft_plan(const ModelConfig& cfg) {
   g.x[0] = wpad; g.xdt = DT_F32; g.ydt = DT_F32;
   g.bstride[0] = Lp; g.rowlen[0] = Lp; g.fstride[0] = hop; g.Tin[0] = 1;
   g.M = B * T; g.Tout = 1; g.Fo = T;
-  g.nseg = 1; g.seg[0] = Seg{0, 0, 0, NFFT, 0};
+  g.nseg = 1;
   g.N = SW;
-  Builder::layout_segs(g);
-  {
-    std::vector<float> wt((size_t)g.Npad * g.ldw, 0.f);
-    for (int nn = 2; nn < g.N; ++nn)
-      for (int j = 0; j < NFFT; ++j) {
-        const double ang = 2.0 * kPi * (double)(((int64_t)(nn / 2 - 1) * j) % NFFT) / NFFT;
-        wt[(size_t)nn * g.ldw + j] = (float)(((nn & 1) == 0 ? std::cos(ang) : -std::sin(ang)) * win[j]);
-      }
-    g.w = b.cst(wt.data(), (int64_t)wt.size() * 4);
-  }
   g.y = spec; g.y_bstride = (int64_t)T * SW; g.y_fstride = SW;
-  b.push(P->fwd, OP_RUNGEMM, 2).g = g;
+  // The sum over a frame's fft_len samples runs in chunks of kChunk, every chunk a GEMM of its own that adds onto the one before (kRunAccum).
+  // One fp32 accumulator walking all the products rounds at the size of the growing partial sum: 6e-7 of the largest bin at fft_len 512, where
+  // float32 torch.stft stays at 1.5e-7; partial sums over 128 samples, added up, keep this GEMM below 3e-7 (tests/test_gpu_frontend_edges.py).
+  constexpr int kChunk = 128;
+  for (int k0 = 0; k0 < NFFT; k0 += kChunk) {
+    RunGemm q = g;
+    const int len = std::min(kChunk, NFFT - k0);
+    q.seg[0] = Seg{0, 0, k0, len, 0};
+    Builder::layout_segs(q);
+    std::vector<float> wt((size_t)q.Npad * q.ldw, 0.f);
+    for (int nn = 2; nn < q.N; ++nn)
+      for (int j = k0; j < k0 + len; ++j) {
+        const double ang = 2.0 * kPi * (double)(((int64_t)(nn / 2 - 1) * j) % NFFT) / NFFT;
+        wt[(size_t)nn * q.ldw + (j - k0)] = (float)(((nn & 1) == 0 ? std::cos(ang) : -std::sin(ang)) * win[j]);
+      }
+    q.w = b.cst(wt.data(), (int64_t)wt.size() * 4);
+    if (k0 > 0) q.flags |= kRunAccum;
+    b.push(P->fwd, OP_RUNGEMM, 2).g = q;
+  }
   SpecOut so;
   std::memset(&so, 0, sizeof(so));
   so.est = spec; so.out_real = io_spec; so.out_imag = b.none(); so.B = B; so.T = T; so.NF = NF; so.mode = 3;
@@ -93,11 +114,24 @@ Plan* build_torchistft_plan(const ModelConfig& cfg) {
   b.c = cfg;
   const int B = cfg.B, L = cfg.L, W = cfg.win_len, hop = cfg.hop, NFFT = cfg.fft_len;
   const int pad = NFFT / 2;
-  const int T = 1 + L / hop;
   const int NF = NFFT / 2 + 1, NS = NF + 1, SW = NS * 2;
-  P->T = T;
   P->NF = NF;
-  if (NFFT != 512 || W > NFFT || pad >= L || (T - 1) * hop + NFFT < pad + L) { P->error = "torch.istft plan: fft_len must be 512 and the frames must cover the clip"; return P; }
+  // one sentence per limit: the message names the one that was hit
+  if (NFFT != 512) {
+    P->error = "torch.istft plan: fft_len " + std::to_string(NFFT) + " is not 512, the only size the inverse-FFT frame kernel is built for";
+    return P;
+  }
+  if (W <= 0 || W > NFFT) {
+    P->error = "torch.istft plan: win_len " + std::to_string(W) + " must lie in 1 .. fft_len = " + std::to_string(NFFT);
+    return P;
+  }
+  if (hop <= 0) { P->error = "torch.istft plan: hop " + std::to_string(hop) + " is not positive"; return P; }
+  if (pad >= L) {
+    P->error = "torch.istft plan: length " + std::to_string(L) + " is not above fft_len/2 = " + std::to_string(pad) + " (no torch.stft has such a clip)";
+    return P;
+  }
+  const int T = 1 + L / hop;
+  P->T = T;
   Ptr io_spec = b.io("spec", (int64_t)B * NF * T * 2);
   Ptr io_wav = b.io("wav", (int64_t)B * L);
   Ptr est = b.ws("est", (int64_t)B * T * SW, DT_F32);
@@ -120,14 +154,26 @@ Plan* build_torchistft_plan(const ModelConfig& cfg) {
     op.ifft.est = est; op.ifft.frames = frames; op.ifft.tw = b.cst(tw.data(), 4096); op.ifft.win = b.win512(win);
     op.ifft.corr = b.cst(c.data(), (int64_t)c.size() * 4); op.ifft.nframes = (int64_t)B * T; op.ifft.W = NFFT;
   }
+  // Window envelope in double, and torch.istft's own test on it: the overlap-add divides by the envelope alone, so a clip that reaches a sample
+  // where it is (next to) zero has no inverse - torch raises there ("window overlap add min"), and so does this plan.  A clip that runs past
+  // the last frame is zero from there on (torch pads it): Ola::Lout, as for ConviSTFT.
   const int Lp = (T - 1) * hop + NFFT;
-  std::vector<float> env(Lp, 0.f);
+  const int Lcov = std::min(L, Lp - pad);
+  std::vector<double> env64(Lp, 0.0);
   for (int t = 0; t < T; ++t)
-    for (int j = 0; j < NFFT; ++j) env[t * hop + j] += (float)(win[j] * win[j]);
+    for (int j = 0; j < NFFT; ++j) env64[t * hop + j] += win[j] * win[j];
+  for (int p = pad; p < pad + Lcov; ++p)
+    if (env64[p] <= 1e-11) {
+      P->error = "torch.istft plan: at length " + std::to_string(L) + " the clip reaches sample " + std::to_string(p - pad) + ", where the overlap-add envelope of the " +
+                 std::to_string(W) + "-sample Hann window at hop " + std::to_string(hop) + " over " + std::to_string(T) + " frames is " + std::to_string(env64[p]) +
+                 " (not above 1e-11): torch.istft refuses this length too";
+      return P;
+    }
+  std::vector<float> env(env64.begin(), env64.end());
   Ola ola;
   std::memset(&ola, 0, sizeof(ola));
   ola.frames = frames; ola.wav = io_wav; ola.coff = b.cst(env.data(), (int64_t)env.size() * 4); ola.dwav = ola.dpad = b.none();
-  ola.B = B; ola.T = T; ola.L = L; ola.win = NFFT; ola.hop = hop; ola.trim = pad; ola.noclamp = 1;
+  ola.B = B; ola.T = T; ola.L = L; ola.win = NFFT; ola.hop = hop; ola.trim = pad; ola.noclamp = 1; ola.Lout = Lcov < L ? Lcov : 0;
   b.push(P->fwd, OP_OLA_FWD, 4).ola = ola;
   finish_plan(b, P, 0, 0);
   return P;

@@ -1134,7 +1134,7 @@ void run_op(const Op& op, const AB& ab) {
           if (d.Lout > 0 && n >= d.Lout) { wav[(int64_t)b * d.L + n] = 0.f; continue; }      // behind the clip ConviSTFT returns
           double s = 0;
           for (int t = 0; t < d.T; ++t) { const int j = p - t * d.hop; if (j >= 0 && j < d.win) s += fr[((int64_t)b * d.T + t) * d.win + j]; }
-          float v = (float)s / (coff[p] + 1e-8f);
+          float v = d.noclamp ? (float)s / coff[p] : (float)s / (coff[p] + 1e-8f);       // torch.istft: the envelope alone (ola_fwd_kernel)
           wav[(int64_t)b * d.L + n] = d.noclamp ? v : std::fmin(1.f, std::fmax(-1.f, v));
         }
       break;
