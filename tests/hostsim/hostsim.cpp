@@ -909,7 +909,9 @@ void run_op(const Op& op, const AB& ab) {
             const int64_t rp_ = (int64_t)g * d.B * T + (d.tmajor ? (int64_t)(tb - 1) * d.B + b : (int64_t)b * T + tb - 1);
             for (int j = 0; j < H; ++j) { h[j] = ld(rp(ab, d.h), d.hdt, rp_ * H + j); c[j] = cs[rp_ * H + j]; }
           }
-          for (int t = tb; t < te; ++t) {
+          const bool rev = (d.rev_mask >> g) & 1;         // reversed group (cluster plans): logical step s is physical frame T - 1 - s
+          for (int s_ = tb; s_ < te; ++s_) {
+            const int t = rev ? T - 1 - s_ : s_;
             const int64_t rt = d.tmajor ? (int64_t)t * d.B + b : (int64_t)b * T + t;      // (sequence, frame) -> row of the buffers
             const int64_t gxo = d.gx_goff[g] + rt * d.gx_ld;
             const int64_t row = (int64_t)g * d.B * T + rt;
@@ -967,13 +969,15 @@ void run_op(const Op& op, const AB& ab) {
         if (d.hdt == DT_BF16) for (auto& x : whh) x = bf2f(f2bf(x));
         for (int b = 0; b < d.B; ++b) {
           std::vector<double> dhrec(H, 0.0), dc(H, 0.0), dg(4 * H);
-          for (int t = T - 1; t >= 0; --t) {
+          const bool rev = (d.rev_mask >> g) & 1;         // reversed group: logical step s is physical frame T - 1 - s, its predecessor the frame after it
+          for (int s_ = T - 1; s_ >= 0; --s_) {
+            const int t = rev ? T - 1 - s_ : s_;
             const int64_t rt = d.tmajor ? (int64_t)t * d.B + b : (int64_t)b * T + t;
-            const int64_t row = (int64_t)g * d.B * T + rt, rowp = row - (d.tmajor ? d.B : 1);
+            const int64_t row = (int64_t)g * d.B * T + rt, rowp = rev ? row + (d.tmajor ? d.B : 1) : row - (d.tmajor ? d.B : 1);
             for (int j = 0; j < H; ++j) {
               const int64_t gq = (row * H + j) * 4;
               const double ig = ld(rp(ab, d.gates), sdt, gq), fg = ld(rp(ab, d.gates), sdt, gq + 1), gg = ld(rp(ab, d.gates), sdt, gq + 2), og = ld(rp(ab, d.gates), sdt, gq + 3);
-              const double ct = cs[row * H + j], cp = t > 0 ? cs[rowp * H + j] : 0.0;
+              const double ct = cs[row * H + j], cp = s_ > 0 ? cs[rowp * H + j] : 0.0;
               double dup;
               if (d.impl == 1 && d.no == 2) {                 // rank-2 upstream gradient from the 2-output head
                 const float* wo = (const float*)rp(ab, d.wo);
@@ -1000,7 +1004,7 @@ void run_op(const Op& op, const AB& ab) {
             for (int k = 0; k < 4 * H; ++k) st(rp(ab, d.dgates), d.gdt, o + gate_col(k / H, k % H), (float)dg[k]);
             for (int j = 0; j < H; ++j) {
               double s = 0;
-              if (t > 0) for (int k = 0; k < 4 * H; ++k) s += (d.hdt == DT_BF16 ? (double)bf2f(f2bf((float)dg[k])) : dg[k]) * whh[(int64_t)k * H + j];
+              if (s_ > 0) for (int k = 0; k < 4 * H; ++k) s += (d.hdt == DT_BF16 ? (double)bf2f(f2bf((float)dg[k])) : dg[k]) * whh[(int64_t)k * H + j];
               dhrec[j] = s;
             }
           }

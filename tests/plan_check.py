@@ -28,7 +28,7 @@ def _tail_noise(B, n):
     return torch.full((B, n), 0.37)
 
 
-def check_dccrn_plan_vs_oracle(mode, loss, kw, B, L, bars=None, report=None, oracle_dtype=torch.float32, kink=None):
+def check_dccrn_plan_vs_oracle(mode, loss, kw, B, L, bars=None, report=None, oracle_dtype=torch.float32, kink=None, params=None):
     """Plan(B, L, masking_mode=mode, **kw) on the host simulator against oracle/dccrn.py.  Depth, bins per layer and hidden dim follow from
     kw (kernel_num, fft_len).  Bars (max-abs over max-abs): spectrum 1e-5, encoder activations 2e-5, decoder activations and outputs 5e-5,
     running statistics 1e-5, gradients 2e-4 (PReLU slopes 2e-3, encoder.0.1.bias 1e-2, conv biases in front of BatchNorm: noise);
@@ -38,9 +38,10 @@ def check_dccrn_plan_vs_oracle(mode, loss, kw, B, L, bars=None, report=None, ora
     gradients the float32 oracle itself does not hold to the bars.
     kink = (decoder layer d, channel c): the oracle's BatchNorm output of that channel has ONE element within fp32 rounding of the PReLU kink (asserted:
     closer to zero than two fp32 ulps of 1), so which branch it takes - and with it the term (1 - slope) * dz of that element in decoder.<d>.1.bias[c] - is
-    decided by the last bit of the statistics.  That tensor must meet its bar against the oracle's gradient with EITHER branch for that one element."""
+    decided by the last bit of the statistics.  That tensor must meet its bar against the oracle's gradient with EITHER branch for that one element.
+    params: {state_dict name: tensor} for the plan AND the oracle instead of the formula weights (recurrence_cases.hot_biases of them)."""
     cfg = dccrn_config(mode, kw)
-    P = formula_state_dict(dccrn_state_shapes(cfg))
+    P = formula_state_dict(dccrn_state_shapes(cfg)) if params is None else params
     plan = Plan(B, L, masking_mode=mode, **kw)
     T, NF = plan.T, plan.NF
     Lout = frames_span(L, cfg.win_len, cfg.win_inc)
@@ -139,13 +140,14 @@ def crn_config(kw):
     return CRNConfig(rnn_input_size=D * (kw["kernel_num"][-1] // 2), **{k: v for k, v in kw.items() if k in ("kernel_num", "rnn_units", "win_len", "win_inc", "fft_len", "masking_mode", "skip_type")})
 
 
-def check_crn_plan_vs_oracle(kw, B, L, bars=None, report=None):
-    """The CRN counterpart (mask mode, SI-SNR on the waveform): Plan(B, L, model="CRN", **kw) on the host simulator against oracle/crn.py, same bars."""
+def check_crn_plan_vs_oracle(kw, B, L, bars=None, report=None, params=None):
+    """The CRN counterpart (mask mode, SI-SNR on the waveform): Plan(B, L, model="CRN", **kw) on the host simulator against oracle/crn.py, same bars;
+    params: as in check_dccrn_plan_vs_oracle."""
     from oracle.crn import crn_forward, crn_state_shapes
     cfg = crn_config(kw)
     kn = tuple(cfg.kernel_num)
     n = len(kn)
-    P = formula_state_dict(crn_state_shapes(cfg))
+    P = formula_state_dict(crn_state_shapes(cfg)) if params is None else params
     plan = Plan(B, L, model="CRN", **kw)
     want = [(k, tuple(v)) for k, v in crn_state_shapes(cfg).items() if is_trainable(k)]
     assert [(k, shp) for k, (off, shp) in plan.params.items()] == want
@@ -202,6 +204,40 @@ def check_crn_plan_vs_oracle(kw, B, L, bars=None, report=None):
     return report
 
 
+def check_fsn_plan_vs_oracle(seq, norm, params=None, report=None):
+    """FullSubNet (hidden sizes 128 / 64, B = 2, 6000 samples, keep 1) on the host simulator against oracle/fullsubnet.py: the complex ratio mask to
+    2e-5, every gradient to 2e-4 (max-abs over max-abs); params: as in check_dccrn_plan_vs_oracle."""
+    from oracle.fullsubnet import FSNConfig, fsn_forward, fsn_state_shapes, fsn_targets
+    hid = (128, 64)
+    cfg = FSNConfig(fb_hidden=hid[0], sb_hidden=hid[1], sequence_model=seq, norm_type=norm)
+    P = formula_state_dict(fsn_state_shapes(cfg)) if params is None else params
+    B, L = 2, 6000
+    x, y = make_signals(B, L)
+    mag, cirm = fsn_targets(x, y, cfg)
+    T = mag.shape[-1]
+    plan = Plan(B, T, model="FullSubNet", fsn=dict(fb_hidden=hid[0], sb_hidden=hid[1], keep=1.0, sequence_model=seq, norm_type=norm))
+    assert [(k, shp) for k, (off, shp) in plan.params.items()] == [(k, tuple(v)) for k, v in fsn_state_shapes(cfg).items()]
+    ar = plan.alloc_arenas("cpu")
+    fill_params(plan, ar, P)
+    plan.io(ar, "mag", (B, 257, T)).copy_(mag)
+    sim_run(plan, PHASE_FWD, ar)
+    Pg = {k: v.clone().requires_grad_(True) for k, v in P.items()}
+    crm = fsn_forward(Pg, mag, cfg)
+    report = {} if report is None else report
+    report["crm"] = rel_err(plan.io(ar, "crm", (B, 257, T, 2)), crm)
+    assert report["crm"] < 2e-5
+    loss = torch.mean((cirm - crm) ** 2)
+    names = list(Pg)
+    grads = dict(zip(names, torch.autograd.grad(loss, [Pg[k] for k in names], retain_graph=True)))
+    plan.io(ar, "grad_crm", (B, 257, T, 2)).copy_(torch.autograd.grad(loss, crm)[0])
+    sim_run(plan, PHASE_BWD, ar)
+    got = read_params(plan, ar, ARENA_GRAD)
+    for k in names:
+        report[k] = rel_err(got[k], grads[k])
+        assert report[k] < 2e-4, (k, report[k])
+    return report
+
+
 # ================================================================================================ GPU: device against simulator, op by op
 KIND = {1: "RUNGEMM", 2: "WGRAD", 3: "PACK", 4: "UNPACK", 5: "BN_FINALIZE", 6: "BN_APPLY", 7: "BN_BWD_REDUCE", 8: "BN_BWD_APPLY",
         9: "LSTM_FWD", 10: "LSTM_BWD", 11: "COMBINE_FWD", 12: "COMBINE_BWD", 13: "MASK_FWD", 14: "MASK_BWD", 15: "OLA_FWD",
@@ -219,11 +255,14 @@ def _typed(t_u8, dt):
     return t_u8.view(torch.bfloat16 if dt == 1 else torch.float32)
 
 
-def ops_device_vs_sim(plan, P, model, B, L, dtype):
+def ops_device_vs_sim(plan, P, model, B, L, dtype, per_element=False):
     """Run every op of both phases of `plan` on the device and on the host simulator from the SAME pre-op state (so an error is localised to
     one launch) and detect writes outside the regions the simulator's op changes.  P: {state_dict name: tensor}; model: DCCRN / DCCRN_CBN / CRN /
-    FullSubNet (L = frames).  Bars, relative to the largest element of the region: fp32 buffers 1e-3, bf16 buffers 1.6e-2 (two bf16 ulps), fp32 state
-    of a bf16 recurrence op and the fp32 `.bnpart` sums of a bf16 GEMM 4e-3.  Returns (report lines, the lines of the ops that miss)."""
+    FullSubNet / SequenceModel (L = frames).  Bars, relative to the largest element of the region: fp32 buffers 1e-3, bf16 buffers 1.6e-2 (two bf16 ulps), fp32 state
+    of a bf16 recurrence op and the fp32 `.bnpart` sums of a bf16 GEMM 4e-3.  per_element (the cases with saturating gate biases only): a region
+    whose largest element exceeds 1 is measured per element, |device - simulator| <= tol * max(1, |simulator|) with the same tol - a bias of 100 in a
+    pre-activation slab or a cell state of 10 must not loosen the bar of every other element of its region.
+    Returns (report lines, the lines of the ops that miss)."""
     dev = plan.alloc_arenas("cuda")
     host = plan.alloc_arenas("cpu")
     fill_params(plan, dev, P)
@@ -231,6 +270,13 @@ def ops_device_vs_sim(plan, P, model, B, L, dtype):
     if model == "FullSubNet":
         plan.io(dev, "mag", (B, 257, L)).copy_(torch.rand(B, 257, L) * 3)
         plan.io(dev, "grad_crm", (B, 257, L, 2)).copy_(torch.randn(B, 257, L, 2) * 1e-3)
+        plan.set_seed(dev, 77)
+    elif model == "SequenceModel":
+        from seqmodel_common import time_major
+        I, O = P["sequence_model.weight_ih_l0"].shape[1], P["fc_output_layer.weight"].shape[0]
+        xt = time_major(torch.rand(B, I, L) * 6)
+        plan.io(dev, "x", tuple(xt.shape)).copy_(xt)
+        plan.io(dev, "grad_y", (L, B, O)).copy_(torch.randn(L, B, O) * 1e-3)
         plan.set_seed(dev, 77)
     else:
         x, y = make_signals(B, L)
@@ -297,7 +343,10 @@ def ops_device_vs_sim(plan, P, model, B, L, dtype):
                     if hchg:
                         hv, gv = _typed(h8[off:off + nb], dt).double(), _typed(g8, dt).double()
                         den = float(hv.abs().max())
-                        err = float((hv - gv).abs().max()) / (den if den > 0 else 1.0)
+                        if per_element and den > 1.0:
+                            err = float(((hv - gv).abs() / hv.abs().clamp(min=1.0)).max())
+                        else:
+                            err = float((hv - gv).abs().max()) / (den if den > 0 else 1.0)
                         if not np.isfinite(err):
                             err = float("inf")
                         tol = 1.6e-2 if dt == 1 else 1e-3

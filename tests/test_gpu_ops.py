@@ -45,6 +45,12 @@ def test_every_op_against_host_simulator(model, B, L, mode, kn, ru, dtype):
     """Tolerances: fp32 buffers 1e-3 (observed <= 3e-6); bf16 buffers 1.6e-2 = two bf16 ulps of the largest element
     (simulator and kernel round slightly different fp32 accumulations of the SAME bf16 operands); fp32 state written by a whole
     bf16 recurrence op (LSTM_FWD / LSTM_BWD): 4e-3 = one bf16 ulp of h fed back through the frames."""
+    every_op_against_host_simulator(model, B, L, mode, kn, ru, dtype)
+
+
+def every_op_against_host_simulator(model, B, L, mode, kn, ru, dtype, params=None, per_element=False, report_prefix="ops_report"):
+    """One row of the table above, steered by its knobs.  params: a function applied to the formula weights {state_dict name: tensor} before they go to
+    the device and the simulator (recurrence_cases.hot_biases); per_element: plan_check.ops_device_vs_sim's rule for such weights."""
     from plan_check import ops_device_vs_sim
     from simutil import Plan
     if L == 2401:                          # the wide-tile kernel needs M >= 4096 by default: lower the bar so that this small case runs it
@@ -91,13 +97,16 @@ def test_every_op_against_host_simulator(model, B, L, mode, kn, ru, dtype):
     knobs.unset("CG256_MINM")        # the plan is built: later tests get the default thresholds again
     knobs.unset("WG256_MINM")
     knobs.unset("LSTM_ROWS_MIN")
-    lines, bad = ops_device_vs_sim(plan, P, model, B, L, dtype)
+    if params is not None:
+        P = params(P)
+    lines, bad = ops_device_vs_sim(plan, P, model, B, L, dtype, per_element=per_element)
     knobs.unset("LSTM_MT")
     knobs.unset("LSTM_RPW")
     knobs.unset("DIRECT_MINM")
-    with open(report_path(f"ops_report_{model}_B{B}_{mode.replace('/', '-')}_{dtype}_{L}.txt"), "w") as f:
+    with open(report_path(f"{report_prefix}_{model}_B{B}_{mode.replace('/', '-')}_{dtype}_{L}.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
     assert not bad, "\n".join(bad[:20])
+    return lines
 
 
 @pytest.mark.parametrize("kind,name", [(0, "MSE"), (1, "SDR"), (2, "SI-SNR"), (3, "SI-SDR")])

@@ -9,7 +9,7 @@ from oracle.dccrn import DCCRNConfig, dccrn_forward, dccrn_state_shapes, is_trai
 from oracle.frontend import analysis_kernel, synthesis_kernel, ola_normaliser
 from oracle.losses import main_loss
 from oracle.weights import formula_state_dict, test_signals as make_signals
-from plan_check import check_crn_plan_vs_oracle, check_dccrn_plan_vs_oracle
+from plan_check import check_crn_plan_vs_oracle, check_dccrn_plan_vs_oracle, check_fsn_plan_vs_oracle
 from simutil import (ARENA_PARAM, PHASE_BWD, PHASE_FWD, Plan, act_to_nchw, fill_params, read_params, sim_run, spec_to_ref)
 from simutil import DEFAULT_KN, DEFAULT_KN_ONLY, KIND_WGRAD, RUN_DY_FROM_BN, check_syncbn_result, unit_slopes
 from sefd_amd.plan import ARENA_GRAD, ARENA_STATE
@@ -362,31 +362,7 @@ def test_crn_direct_mode_hostsim_vs_oracle():
                                       ("GRU", "offline_gaussian_norm"), ("LSTM", "cumulative_layer_norm")])
 def test_fsn_hostsim_forward_backward_vs_oracle(seq, norm):
     """cfg.sequence_model (tools_for_model.py:739-756) and cfg.norm_type (:1106-1118) variants of the FullSubNet plan."""
-    from oracle.fullsubnet import FSNConfig, fsn_forward, fsn_state_shapes, fsn_targets
-    hid = (128, 64)
-    cfg = FSNConfig(fb_hidden=hid[0], sb_hidden=hid[1], sequence_model=seq, norm_type=norm)
-    P = formula_state_dict(fsn_state_shapes(cfg))
-    B, L = 2, 6000
-    x, y = make_signals(B, L)
-    mag, cirm = fsn_targets(x, y, cfg)
-    T = mag.shape[-1]
-    plan = Plan(B, T, model="FullSubNet", fsn=dict(fb_hidden=hid[0], sb_hidden=hid[1], keep=1.0, sequence_model=seq, norm_type=norm))
-    assert [(k, shp) for k, (off, shp) in plan.params.items()] == [(k, tuple(v)) for k, v in fsn_state_shapes(cfg).items()]
-    ar = plan.alloc_arenas("cpu")
-    fill_params(plan, ar, P)
-    plan.io(ar, "mag", (B, 257, T)).copy_(mag)
-    sim_run(plan, PHASE_FWD, ar)
-    Pg = {k: v.clone().requires_grad_(True) for k, v in P.items()}
-    crm = fsn_forward(Pg, mag, cfg)
-    assert rel_err(plan.io(ar, "crm", (B, 257, T, 2)), crm) < 2e-5
-    loss = torch.mean((cirm - crm) ** 2)
-    names = list(Pg)
-    grads = dict(zip(names, torch.autograd.grad(loss, [Pg[k] for k in names], retain_graph=True)))
-    plan.io(ar, "grad_crm", (B, 257, T, 2)).copy_(torch.autograd.grad(loss, crm)[0])
-    sim_run(plan, PHASE_BWD, ar)
-    got = read_params(plan, ar, ARENA_GRAD)
-    for k in names:
-        assert rel_err(got[k], grads[k]) < 2e-4, k
+    check_fsn_plan_vs_oracle(seq, norm)
 
 
 def test_fsn_bf16_cluster_lstm_plan_equals_the_per_step_plan(monkeypatch):
