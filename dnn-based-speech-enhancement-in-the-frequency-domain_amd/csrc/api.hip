@@ -130,6 +130,12 @@ int32_t sefd_plan_op_info(const sefd_plan* h, int phase, int i, int64_t* o) {
   } else if (op.kind == OP_ISTFT_FFT) {
     o[2] = op.ifft.nframes; o[3] = op.ifft.W; o[4] = 512;
     o[7] = op.ifft.nframes * (258 * 8 + (int64_t)op.ifft.W * 4);
+  } else if (op.kind == OP_IFFT_OLA) {                                     // M = frames a workgroup owns, N = halo frames it recomputes
+    const IfftOla& f = op.iola;
+    o[2] = f.fpw; o[3] = f.halo; o[4] = 512;
+    o[7] = (int64_t)f.B * f.T * 258 * 8 + (int64_t)f.B * f.Lout * 4;
+  } else if (op.kind == OP_SPECCONV) {
+    o[2] = (int64_t)op.sc.B * op.sc.T; o[3] = op.sc.NF; o[5] = (int64_t)op.sc.mode << 8;
   }
   return 0;
 }

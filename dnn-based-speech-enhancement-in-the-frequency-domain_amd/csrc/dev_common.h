@@ -201,6 +201,8 @@ bool launch_rundirect(const RunGemm& d, const ArenaBases& ab, hipStream_t st);  
 void launch_misc(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st);
 void launch_istft_fft(const IstftFft& d, const ArenaBases& ab, hipStream_t st);
+void launch_ifft_ola(const IfftOla& d, const ArenaBases& ab, hipStream_t st);   // fused inverse FFT + overlap-add (stft_fft.hip)
+void launch_specconv(const SpecConv& d, const ArenaBases& ab, hipStream_t st);   // ConvSTFT / ConviSTFT spectrum conversions (stft_fft.hip)
 void launch_fsn(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_bn(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_cbn(const Op& op, const ArenaBases& ab, hipStream_t st);       // ComplexBatchNorm (cbn.hip)

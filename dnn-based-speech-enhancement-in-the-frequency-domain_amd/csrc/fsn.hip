@@ -579,6 +579,7 @@ void launch_fsn(const Op& op, const ArenaBases& ab, hipStream_t st) {
   switch (op.kind) {
     case OP_STFT_FFT: launch_stft_fft(op.fft, ab, st); break;
     case OP_ISTFT_FFT: launch_istft_fft(op.ifft, ab, st); break;
+    case OP_IFFT_OLA: launch_ifft_ola(op.iola, ab, st); break;
     case OP_REFLECTPAD: hipLaunchKernelGGL(reflectpad_kernel, dim3(gridn((int64_t)op.rpad.B * (op.rpad.L + 2 * op.rpad.pad))), dim3(256), 0, st, op.rpad, ab); break;
     case OP_CELL_FWD:
       if (op.cell.kind == 1) hipLaunchKernelGGL(gru_fwd_kernel, dim3(gridn(op.cell.rows * op.cell.H)), dim3(256), 0, st, op.cell, ab);

@@ -736,7 +736,7 @@ __global__ void ola_fwd_kernel(const Ola d, const ArenaBases ab) {
     for (int t = t0; t <= t1; ++t) s += fr[((int64_t)b * d.T + t) * d.win + (p - t * d.hop)];
     // noclamp = the torch.istft plan: torch divides by the envelope alone (its planner refuses a clip that reaches an envelope of zero);
     // the 1e-8 is ConviSTFT's (DCCRN / CRN), and at the last samples of a clip it is as large as the envelope itself
-    s = d.noclamp ? s / coff[p] : s / (coff[p] + 1e-8f);
+    s = d.noclamp == 1 ? s / coff[p] : s / (coff[p] + 1e-8f);
     wav[i] = d.noclamp ? s : fminf(1.f, fmaxf(-1.f, s));
   }
 }
@@ -752,7 +752,9 @@ __global__ void ola_bwd_kernel(const Ola d, const ArenaBases ab) {
     const int p = (int)(i - b * Lp);
     float v = 0.f;
     const int s = p - d.trim;
-    if (s >= 0 && s < (d.Lout > 0 ? d.Lout : d.L)) {
+    if (d.noclamp == 2) {                                   // ConviSTFT on its own: no clamp, every sample passes its gradient
+      if (s >= 0 && s < (d.Lout > 0 ? d.Lout : d.L)) v = dwav[b * d.L + s] / (coff[p] + 1e-8f);
+    } else if (s >= 0 && s < (d.Lout > 0 ? d.Lout : d.L)) {
       const float w = wav[b * d.L + s];
       // clamp_ passes the gradient where the un-clamped value lies in [-1, 1]; a clamped sample equals +-1 exactly
       if (w > -1.f && w < 1.f) v = dwav[b * d.L + s] / (coff[p] + 1e-8f);
@@ -1074,6 +1076,7 @@ void launch_misc(const Op& op, const ArenaBases& ab, hipStream_t st) {
       hipLaunchKernelGGL(specpad_kernel, dim3(grid_for(op.mags.frames * op.mags.NF * op.mags.MS)), dim3(256), 0, st, op.mags, ab); break;
     case OP_MAGS:
       hipLaunchKernelGGL(mags_kernel, dim3(grid_for(op.mags.frames * op.mags.MS)), dim3(256), 0, st, op.mags, ab); break;
+    case OP_SPECCONV: launch_specconv(op.sc, ab, st); break;
     case OP_MEMSET:
       (void)hipMemsetAsync(rp(ab, op.ms.dst), 0, op.ms.bytes, st); break;
     default: launch_fsn(op, ab, st); break;

@@ -1,4 +1,4 @@
-// Front-end planners: the ConvSTFT front end on its own, torch.stft and torch.istft.
+// Front-end planners: the ConvSTFT front end on its own, torch.stft and torch.istft, and ConvSTFT / ConviSTFT as differentiable modules.
 #include "plan_builder.h"
 
 namespace sefd {
@@ -175,6 +175,202 @@ Plan* build_torchistft_plan(const ModelConfig& cfg) {
   ola.frames = frames; ola.wav = io_wav; ola.coff = b.cst(env.data(), (int64_t)env.size() * 4); ola.dwav = ola.dpad = b.none();
   ola.B = B; ola.T = T; ola.L = L; ola.win = NFFT; ola.hop = hop; ola.trim = pad; ola.noclamp = 1; ola.Lout = Lcov < L ? Lcov : 0;
   b.push(P->fwd, OP_OLA_FWD, 4).ola = ola;
+  finish_plan(b, P, 0, 0);
+  return P;
+}
+
+// =================================================================================================================
+// ConvSTFT (model 7) and ConviSTFT (model 8) on their own (tools_for_model.py:36-112): each a forward and a backward phase.
+// kernel_num[0] = feature type: 0 'complex' (the concatenated [B][2 NF][T] tensor), 1 anything else ((mags, phase), [B][NF][T] each).
+namespace {
+
+// One sentence per limit; true when the geometry was refused.
+bool convstft_refuse(Plan* P, const char* who, const ModelConfig& cfg) {
+  const int W = cfg.win_len, hop = cfg.hop, NFFT = cfg.fft_len;
+  const std::string pre = std::string(who) + " plan: ";
+  if (W < 1 || NFFT < 2 || NFFT % 2 != 0) { P->error = pre + "win_len " + std::to_string(W) + " / fft_len " + std::to_string(NFFT) + " must be positive and fft_len even"; return true; }
+  if (W > NFFT) { P->error = pre + "win_len " + std::to_string(W) + " is above fft_len " + std::to_string(NFFT) + " (the analysis basis has fft_len rows only)"; return true; }
+  if (hop <= 0 || hop > W) { P->error = pre + "hop " + std::to_string(hop) + " must lie in 1 .. win_len = " + std::to_string(W); return true; }
+  if (cfg.B < 1) { P->error = pre + "batch " + std::to_string(cfg.B) + " is not positive"; return true; }
+  return false;
+}
+
+// Frames per workgroup of the fused inverse-FFT + overlap-add kernel: 16, halved until the staged frames (halo included) fit 40 KiB of LDS
+// beside the kernel's 22 KiB of transform slices and twiddles (64 KiB per workgroup).  0: they do not fit (take the two-launch composition).
+int ifft_ola_fpw(int W, int hop) {
+  const int halo = (W + hop - 1) / hop - 1;
+  for (int fpw = 16; fpw >= 4; fpw /= 2)
+    if ((int64_t)(halo + fpw) * W * 4 <= 40 * 1024) return fpw;
+  return 0;
+}
+
+// est [B*T][SW] -> out [B][Lout], fft_len == 512: the fused kernel, on the knob CONVSTFT_FUSE and if its stage fits.  False: not planned - the caller plans the
+// two-launch composition, which measured faster (profiles/convstft_bench.json) and is the default.
+bool ifft_ola(Builder& b, std::vector<Op>& ops, int tag, Ptr est, Ptr out, int Lout, bool synth) {
+  const Stft& fe = b.fe;
+  const int fpw = ifft_ola_fpw(fe.W, fe.hop);
+  if (fe.NFFT != 512 || tune_has("STFT_GEMM") || !tune_has("CONVSTFT_FUSE") || fpw == 0) return false;
+  Op& op = b.push(ops, OP_IFFT_OLA, tag);
+  IfftOla& d = op.iola;
+  d.est = est; d.out = out; d.tw = b.fft_tw; d.win = b.win512(fe.win);
+  d.corr = synth ? b.istft_corr(fe.W) : b.none();
+  d.coff = synth ? fe.c_coff : b.none();
+  d.B = fe.B; d.T = fe.T; d.W = fe.W; d.hop = fe.hop; d.trim = fe.trim; d.Lout = Lout;
+  d.fpw = fpw; d.halo = (fe.W + fe.hop - 1) / fe.hop - 1;
+  d.scale = synth ? 1.f / 256.f : 1.f;
+  return true;
+}
+
+void fft_twiddles(Builder& b) {
+  if (b.fft_tw.arena >= 0) return;
+  std::vector<float> tw(1024);
+  for (int k = 0; k < 512; ++k) { tw[2 * k] = (float)std::cos(2.0 * kPi * k / 512.0); tw[2 * k + 1] = (float)std::sin(2.0 * kPi * k / 512.0); }
+  b.fft_tw = b.cst(tw.data(), 4096);
+}
+
+SpecConv specconv(Builder& b, int mode, Ptr spec, Ptr a, Ptr bb) {
+  SpecConv c;
+  std::memset(&c, 0, sizeof(c));
+  c.spec = spec; c.a = a; c.b = bb; c.dspec = c.ga = c.gb = b.none();
+  c.B = b.fe.B; c.T = b.fe.T; c.NF = b.fe.NF; c.mode = mode;
+  return c;
+}
+
+}  // namespace
+
+// ConvSTFT: io.wav [B][L] -> io.out [B][2 NF][T] ('complex') or io.mags, io.phase [B][NF][T]; backward io.grad_out / io.grad_mags, io.grad_phase -> io.grad_wav.
+// Backward = the adjoint of the analysis transform: d wav[b][p] = sum_t win[j] Re sum_k (g_re + i g_im)[k, t] e^{+2 pi i k j / fft_len}, j = p + trim - t hop:
+// the synthesis transform without its rank-2 correction, overlap-added without a normaliser.
+Plan* build_convstft_plan(const ModelConfig& cfg) {
+  Plan* P = new Plan();
+  P->cfg = cfg;
+  P->T = 0; P->NF = cfg.fft_len / 2 + 1;
+  if (convstft_refuse(P, "ConvSTFT", cfg)) return P;
+  Builder b;
+  b.P = P;
+  b.c = cfg;
+  b.fe = Stft(cfg);
+  const Stft& fe = b.fe;
+  const int B = cfg.B, L = cfg.L, T = fe.T, NF = fe.NF, W = fe.W;
+  if (L < 1 || L + 2 * fe.trim < W || T < 1) {
+    P->error = "ConvSTFT plan: a clip of " + std::to_string(L) + " samples gives no frame (T < 1) at win_len " + std::to_string(W) + ", hop " + std::to_string(fe.hop);
+    return P;
+  }
+  P->T = T;
+  const bool polar = cfg.kernel_num[0] != 0;
+  const int64_t BT = (int64_t)B * T;
+  Ptr io_wav = b.io("wav", (int64_t)B * L);
+  Ptr o_a, o_b = b.none(), g_a, g_b = b.none();
+  if (polar) {
+    o_a = b.io("mags", BT * NF); o_b = b.io("phase", BT * NF);
+    g_a = b.io("grad_mags", BT * NF); g_b = b.io("grad_phase", BT * NF);
+  } else {
+    o_a = b.io("out", BT * 2 * NF); g_a = b.io("grad_out", BT * 2 * NF);
+  }
+  Ptr io_gw = b.io("grad_wav", (int64_t)B * L);
+  Ptr spec = b.ws("spec", BT * fe.SW, DT_F32);
+  Ptr gspec = b.ws("gspec", BT * fe.SW, DT_F32);
+  b.stft_fwd(P->fwd, 1, io_wav, spec);
+  b.push(P->fwd, OP_SPECCONV, 2).sc = specconv(b, polar ? 2 : 0, spec, o_a, o_b);
+  {
+    SpecConv c = specconv(b, polar ? 3 : 1, polar ? spec : gspec, g_a, g_b);
+    c.dspec = polar ? gspec : b.none();
+    b.push(P->bwd, OP_SPECCONV, 2).sc = c;
+  }
+  fft_twiddles(b);
+  if (!ifft_ola(b, P->bwd, 1, gspec, io_gw, L, false)) {
+    // the composition: frames [B*T][W] in HBM, then the overlap-add with a normaliser table of ones (its division is then exact)
+    Ptr frames = b.ws("frames", BT * W, DT_F32);
+    if (fe.NFFT == 512 && !tune_has("STFT_GEMM")) {
+      std::vector<double> w256(fe.win);
+      for (double& v : w256) v *= 256.0;                      // the frame kernel's fixed 1/256 (a power of two: exact)
+      std::vector<float> zc(4 * 257, 0.f);
+      Op& op = b.push(P->bwd, OP_ISTFT_FFT, 1);
+      op.ifft.est = gspec; op.ifft.frames = frames; op.ifft.tw = b.fft_tw; op.ifft.win = b.win512(w256);
+      op.ifft.corr = b.cst(zc.data(), (int64_t)zc.size() * 4); op.ifft.nframes = BT; op.ifft.W = W;
+    } else {
+      RunGemm g = Builder::gemm0();                           // the transpose of the framing GEMM
+      g.x[0] = gspec; g.xdt = DT_F32; g.ydt = DT_F32;
+      g.bstride[0] = (int64_t)T * fe.SW; g.tstride[0] = fe.SW; g.rowlen[0] = fe.SW; g.Tin[0] = T;
+      g.M = (int)BT; g.Tout = T; g.Fo = 1;
+      g.nseg = 1; g.seg[0] = Seg{0, 0, 0, fe.SW, 0};
+      g.N = W;
+      Builder::layout_segs(g);
+      b.const_weights(g, [&](int nn, int j) { return j < 2 ? 0.0 : fe.Kun(j & 1, j / 2 - 1, nn) * fe.win[nn]; });
+      g.y = frames; g.y_bstride = (int64_t)T * W; g.y_tstride = W;
+      b.push(P->bwd, OP_RUNGEMM, 1).g = g;
+    }
+    std::vector<float> ones((size_t)std::max(fe.Lp, L + fe.trim), 1.f);
+    Ola ola;
+    std::memset(&ola, 0, sizeof(ola));
+    ola.frames = frames; ola.wav = io_gw; ola.coff = b.cst(ones.data(), (int64_t)ones.size() * 4); ola.dwav = ola.dpad = b.none();
+    ola.B = B; ola.T = T; ola.L = L; ola.win = W; ola.hop = fe.hop; ola.trim = fe.trim; ola.noclamp = 1;
+    b.push(P->bwd, OP_OLA_FWD, 1).ola = ola;
+  }
+  finish_plan(b, P, 0, 0);
+  return P;
+}
+
+// ConviSTFT: cfg.L = frames T (the FullSubNet convention).  io.in [B][2 NF][T] ('complex') or io.mags, io.phase [B][NF][T] -> io.wav [B][Lout],
+// Lout = (T - 1) hop + win_len - 2 (win_len - hop); no clamp, division by coff + 1e-8.  Backward io.grad_wav -> io.grad_in / io.grad_mags, io.grad_phase.
+Plan* build_convistft_plan(const ModelConfig& cfg) {
+  Plan* P = new Plan();
+  P->cfg = cfg;
+  P->T = 0; P->NF = cfg.fft_len / 2 + 1;
+  if (convstft_refuse(P, "ConviSTFT", cfg)) return P;
+  const int B = cfg.B, T = cfg.L, W = cfg.win_len, hop = cfg.hop, trim = W - hop;
+  if (T < 1) { P->error = "ConviSTFT plan: " + std::to_string(T) + " frames (T < 1)"; return P; }
+  const int64_t Lout64 = (int64_t)(T - 1) * hop + W - 2 * (int64_t)trim;
+  if (Lout64 <= 0) {
+    P->error = "ConviSTFT plan: " + std::to_string(T) + " frames at win_len " + std::to_string(W) + ", hop " + std::to_string(hop) + " leave Lout = " +
+               std::to_string(Lout64) + " <= 0 samples after the trim (the reference returns an empty tensor)";
+    return P;
+  }
+  const int Lout = (int)Lout64;
+  ModelConfig fc = cfg;
+  fc.L = Lout;                                                // the clip length whose ConvSTFT has exactly T frames
+  Builder b;
+  b.P = P;
+  b.c = cfg;
+  b.fe = Stft(fc);
+  const Stft& fe = b.fe;
+  const int NF = fe.NF;
+  if (fe.T != T || fe.Lp - 2 * fe.trim != Lout) { P->error = "ConviSTFT plan: frame geometry"; return P; }
+  P->T = T;
+  b.synthesis();
+  const bool polar = cfg.kernel_num[0] != 0;
+  const int64_t BT = (int64_t)B * T;
+  Ptr i_a, i_b = b.none(), g_a, g_b = b.none();
+  if (polar) {
+    i_a = b.io("mags", BT * NF); i_b = b.io("phase", BT * NF);
+    g_a = b.io("grad_mags", BT * NF); g_b = b.io("grad_phase", BT * NF);
+  } else {
+    i_a = b.io("in", BT * 2 * NF); g_a = b.io("grad_in", BT * 2 * NF);
+  }
+  Ptr io_wav = b.io("wav", (int64_t)B * Lout);
+  Ptr io_gw = b.io("grad_wav", (int64_t)B * Lout);
+  Ptr est = b.ws("est", BT * fe.SW, DT_F32);
+  b.push(P->fwd, OP_SPECCONV, 2).sc = specconv(b, polar ? 4 : 1, est, i_a, i_b);
+  fft_twiddles(b);
+  Ola ola;
+  if (ifft_ola(b, P->fwd, 1, est, io_wav, Lout, true)) {
+    std::memset(&ola, 0, sizeof(ola));
+    ola.frames = b.none(); ola.wav = io_wav; ola.coff = fe.c_coff; ola.dwav = ola.dpad = b.none();
+    ola.B = B; ola.T = T; ola.L = Lout; ola.win = W; ola.hop = hop; ola.trim = trim;
+  } else {
+    Ptr frames = b.ws("frames", BT * W, DT_F32);
+    const size_t at = P->fwd.size();
+    ola = b.istft_ola(P->fwd, est, frames, io_wav);
+    for (size_t i = at; i < P->fwd.size(); ++i)
+      if (P->fwd[i].kind == OP_OLA_FWD) P->fwd[i].ola.noclamp = 2;
+  }
+  ola.noclamp = 2;
+  Ptr dest = b.istft_ola_bwd(P->bwd, ola, io_gw);
+  {
+    SpecConv c = specconv(b, polar ? 5 : 0, dest, polar ? i_a : g_a, polar ? i_b : b.none());
+    if (polar) { c.ga = g_a; c.gb = g_b; }
+    b.push(P->bwd, OP_SPECCONV, 2).sc = c;
+  }
   finish_plan(b, P, 0, 0);
   return P;
 }

@@ -305,7 +305,8 @@ struct Ola {
   Ptr frames, wav, coff;
   Ptr dwav, dpad;              // backward: dpad [B][(T-1)*hop+win] = clampmask*dwav/(coff+1e-8) (0 in the trimmed borders)
   int32_t B, T, L, win, hop, trim;
-  int32_t noclamp, Lout;       // noclamp = 1: torch.istft semantics (no clamp_(-1, 1)); the ConviSTFT path of DCCRN / CRN clamps
+  int32_t noclamp, Lout;       // noclamp = 1: torch.istft semantics (no clamp_(-1, 1), division by coff alone); the ConviSTFT path of DCCRN / CRN clamps
+                               // noclamp = 2: ConviSTFT on its own (tools_for_model.py:101-110): no clamp, but coff + 1e-8; its backward does not read wav
                                // Lout > 0: ConviSTFT returned only the first Lout < L samples (the hop does not tile the clip): the rest of wav is 0, its dwav unread
 };
 
@@ -347,6 +348,31 @@ struct IstftFft {
   Ptr est, frames, tw, win, corr;
   int64_t nframes;
   int32_t W, pad_;
+};
+// Fused inverse 512-point FFT + window + overlap-add (stft_fft.hip ifft_ola_kernel): IstftFft's transform and Ola's gather in one launch, the
+// [B*T][W] frames staged in LDS only.  out[b][s] = norm(p) * sum_t frame_t[p - t * hop], p = s + trim, s < Lout, with
+//   frame_t[j] = scale * win[j] * ( Re sum_{k<=256} X_t[k] e^{+2 pi i k j / 512} - C_parity(j) )   (corr = A_NONE: C = 0)
+//   norm(p) = 1 / (coff[p] + 1e-8)                                                              (coff = A_NONE: 1)
+// corr + coff: ConviSTFT.forward without the clamp; neither: the adjoint of the analysis transform (ConvSTFT's backward, scale = 1).
+// A workgroup owns `fpw` consecutive frames of ONE clip and the samples p in [t0 * hop, (t0 + fpw) * hop) (the clip's last run: to the end);
+// it recomputes the halo = ceil(W / hop) - 1 frames to the left of its run.  Samples are summed in frame order: no atomics.
+struct IfftOla {
+  Ptr est, out, tw, win, corr, coff;
+  int32_t B, T, W, hop, trim, Lout;
+  int32_t fpw, halo;
+  float scale;
+  int32_t pad_;
+};
+// Spectrum layout / coordinate conversions of ConvSTFT and ConviSTFT on their own: the slot layout spec [B][T][NF+1][2] against the reference's
+// [B][.][T] arrays (32 x 32 LDS-transposed tiles as SpecOut).  a / b: [B][NF][T] each, or for modes 0 / 1 a alone = [B][2 NF][T] (real block, imaginary block).
+//   0 spec -> a (concatenated)                           1 a (concatenated) -> spec
+//   2 spec -> a = sqrt(re^2 + im^2), b = atan2(im, re)   3 spec, a = g_mags, b = g_phase -> dspec: d re = g_m re / m - g_p (im / m) / m,
+//                                                          d im = g_m im / m + g_p (re / m) / m; both 0 where m == 0 (the reference: NaN)
+//   4 a = mags, b = phase -> spec = m (cos, sin)(ph)      5 spec = (g_re, g_im), a = mags, b = phase -> ga = g_re cos + g_im sin, gb = m (g_im cos - g_re sin)
+// Modes 1, 3, 4 write slot 0 of every frame as zero.
+struct SpecConv {
+  Ptr spec, a, b, dspec, ga, gb;
+  int32_t B, T, NF, mode;
 };
 // torch.stft(center=True, pad_mode='reflect'): dst[b][i] = src[b][reflect(i - pad)], i < L + 2*pad
 struct ReflectPad {
@@ -441,6 +467,8 @@ enum OpKind : int32_t {
   OP_FSN_NORMSTAT, OP_FSN_NORMBWD,   // cfg.norm_type other than offline_laplace_norm (struct Fsn)
   OP_CBN_STATS, OP_CBN_FINALIZE, OP_CBN_APPLY, OP_CBN_BWD_REDUCE, OP_CBN_BWD_FINALIZE, OP_CBN_BWD_APPLY,   // ComplexBatchNorm (CbnFwd / CbnBwd)
   OP_FSN_ACT,                        // Tanh / ReLU6 of FullSubNet's full-band head (struct Fsn)
+  OP_IFFT_OLA,                       // fused inverse FFT + window + overlap-add (struct IfftOla)
+  OP_SPECCONV,                       // ConvSTFT / ConviSTFT spectrum conversions (struct SpecConv)
 };
 
 constexpr int kOpHold = 2;     // Op::join of a lane-1 op
@@ -480,6 +508,8 @@ struct Op {
     PackMulti packm;
     CbnFwd cbf;
     CbnBwd cbb;
+    IfftOla iola;
+    SpecConv sc;
   };
 };
 

@@ -321,6 +321,155 @@ __global__ __launch_bounds__(256) void istft_fft_kernel(const IstftFft d, const 
   }
 }
 
+// Fused inverse FFT + window + overlap-add (struct IfftOla): istft_fft_kernel's transform, one wavefront per frame, into an LDS stage of the workgroup's
+// frames instead of the [B*T][W] HBM buffer, then ola_fwd_kernel's gather from that stage.  A workgroup owns fpw frames of one clip (a run never
+// crosses a clip boundary) and the hop-aligned samples they start; the halo frames to the left that reach into those samples are recomputed.
+// Every output sample is written exactly once, summed over its frames in frame order: the result is bit-identical run to run.  Planned on the knob
+// CONVSTFT_FUSE only: the two-launch composition measured faster.  LDS: 18 KiB transform slices + 4 KiB twiddles + (halo + fpw) * W * 4 B stage (planner: <= 40 KiB).
+__global__ __launch_bounds__(256) void ifft_ola_kernel(const IfftOla d, const ArenaBases ab) {
+  __shared__ float2 lds[4][kFftSlice];
+  __shared__ float2 twl[512];
+  extern __shared__ float stage[];                           // [halo + fpw][W]
+  const float2* est = reinterpret_cast<const float2*>(rp(ab, d.est));
+  const float* win = reinterpret_cast<const float*>(rp(ab, d.win));
+  const float* cr = d.corr.arena >= 0 ? reinterpret_cast<const float*>(rp(ab, d.corr)) : nullptr;
+  const float* coff = d.coff.arena >= 0 ? reinterpret_cast<const float*>(rp(ab, d.coff)) : nullptr;
+  const float2* tw = reinterpret_cast<const float2*>(rp(ab, d.tw));
+  float* out = reinterpret_cast<float*>(rp(ab, d.out));
+  for (int i = threadIdx.x; i < 512; i += 256) twl[i] = tw[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int runs = (d.T + d.fpw - 1) / d.fpw;
+  const int b = blockIdx.x / runs, r = blockIdx.x - b * runs;
+  const int t0 = r * d.fpw;
+  const int tb = t0 - d.halo > 0 ? t0 - d.halo : 0, te = t0 + d.fpw < d.T ? t0 + d.fpw : d.T;
+  const int k0 = lane >> 3, ma = lane & 7;
+  for (int t = tb + wv; t < te; t += 4) {                    // wave-uniform: no wave leaves before the barrier below
+    const float2* in = est + ((int64_t)b * d.T + t) * 258 + 1;
+    cf x[8], X[8];
+    float ce = 0.f, co = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int k = lane + 64 * j;
+      float2 v = make_float2(0.f, 0.f);
+      if (k <= 256) {
+        v = in[k];
+        if (cr) {
+          ce += v.x * cr[k] + v.y * cr[257 + k];
+          co += v.x * cr[2 * 257 + k] + v.y * cr[3 * 257 + k];
+        }
+      }
+      x[j] = {v.x, -v.y};                                    // inverse transform = conj(DFT(conj Y)); only the real part is needed
+    }
+    if (cr) { ce = wave_sum(ce); co = wave_sum(co); }
+    fft512_wave(x, X, lds[wv], twl, lane);
+    float* buf = reinterpret_cast<float*>(lds[wv]);
+    float* row = stage + (t - tb) * d.W;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int mb = 0; mb < 8; ++mb) buf[k0 + 8 * ma + 64 * mb] = X[mb].x;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int j = lane + 64 * i;
+      if (j < d.W) row[j] = (buf[j] - ((j & 1) ? co : ce)) * win[j] * d.scale;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the wave's LDS slice is reused by its next frame
+  }
+  __syncthreads();
+  // samples p (padded coordinate) this run owns, cut to the ones the output keeps: s = p - trim in [0, Lout)
+  int p_lo = t0 * d.hop, p_hi = te == d.T ? d.trim + d.Lout : (t0 + d.fpw) * d.hop;
+  if (p_lo < d.trim) p_lo = d.trim;
+  if (p_hi > d.trim + d.Lout) p_hi = d.trim + d.Lout;
+  for (int p = p_lo + (int)threadIdx.x; p < p_hi; p += 256) {
+    int t1 = p / d.hop; if (t1 > d.T - 1) t1 = d.T - 1;
+    int ta = (p - d.W + d.hop) / d.hop; if (p - d.W + 1 <= 0) ta = 0;        // first frame that reaches p: >= t0 - halo
+    float s = 0.f;
+    for (int t = ta; t <= t1; ++t) s += stage[(t - tb) * d.W + (p - t * d.hop)];
+    if (coff) s = s / (coff[p] + 1e-8f);
+    out[(int64_t)b * d.Lout + (p - d.trim)] = s;
+  }
+}
+
+// ConvSTFT / ConviSTFT spectrum conversions (struct SpecConv): 32 x 32 tiles over (t, bin), transposed through LDS so that both the slot layout
+// (bins adjacent) and the reference layouts (frames adjacent) are read and written in whole lines.  cosf / sinf / atan2f are the accurate library
+// functions: a phase that is a sum of phases leaves [-pi, pi], where the fast intrinsics lose their accuracy.
+__global__ __launch_bounds__(256) void specconv_kernel(const SpecConv d, const ArenaBases ab) {
+  __shared__ float tr[32][33], ti[32][33];
+  const int NS = d.NF + 1, NF = d.NF, T = d.T;
+  const int b = blockIdx.z, t0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const bool to_ref = d.mode == 0 || d.mode == 2 || d.mode == 5;
+  float* spec = reinterpret_cast<float*>(rp(ab, d.spec));
+  float* pa = reinterpret_cast<float*>(rp(ab, d.a));
+  float* pb = d.b.arena >= 0 ? reinterpret_cast<float*>(rp(ab, d.b)) : nullptr;
+  if (to_ref) {
+    for (int r = ty; r < 32; r += 8) {
+      const int t = t0 + r, k = k0 + tx;
+      float vr = 0.f, vi = 0.f;
+      if (t < T && k < NF) {
+        const int64_t o = (((int64_t)b * T + t) * NS + k + 1) * 2;
+        vr = spec[o]; vi = spec[o + 1];
+      }
+      tr[r][tx] = vr; ti[r][tx] = vi;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {
+      const int k = k0 + r, t = t0 + tx;
+      if (t >= T || k >= NF) continue;
+      const float vr = tr[tx][r], vi = ti[tx][r];
+      const int64_t o = ((int64_t)b * NF + k) * T + t;
+      if (d.mode == 0) {
+        pa[((int64_t)b * 2 * NF + k) * T + t] = vr;
+        pa[((int64_t)b * 2 * NF + NF + k) * T + t] = vi;
+      } else if (d.mode == 2) {
+        pa[o] = sqrtf(vr * vr + vi * vi);
+        pb[o] = atan2f(vi == 0.f ? 0.f : vi, vr == 0.f ? 0.f : vr);      // a transform's zero may be -0: atan2(0, -0) would be pi, the reference's conv sums to +0
+      } else {
+        float* ga = reinterpret_cast<float*>(rp(ab, d.ga));
+        float* gb = reinterpret_cast<float*>(rp(ab, d.gb));
+        const float m = pa[o], ph = pb[o], c = cosf(ph), s = sinf(ph);
+        ga[o] = vr * c + vi * s;
+        gb[o] = m * (vi * c - vr * s);
+      }
+    }
+  } else {
+    for (int r = ty; r < 32; r += 8) {
+      const int k = k0 + r, t = t0 + tx;
+      float vr = 0.f, vi = 0.f;
+      if (t < T && k < NF) {
+        const int64_t o = ((int64_t)b * NF + k) * T + t;
+        if (d.mode == 1) {
+          vr = pa[((int64_t)b * 2 * NF + k) * T + t];
+          vi = pa[((int64_t)b * 2 * NF + NF + k) * T + t];
+        } else if (d.mode == 3) {
+          vr = pa[o]; vi = pb[o];
+        } else {
+          const float m = pa[o], ph = pb[o];
+          vr = m * cosf(ph); vi = m * sinf(ph);
+        }
+      }
+      tr[r][tx] = vr; ti[r][tx] = vi;
+    }
+    __syncthreads();
+    float* dst = d.mode == 3 ? reinterpret_cast<float*>(rp(ab, d.dspec)) : spec;
+    for (int r = ty; r < 32; r += 8) {
+      const int t = t0 + r, k = k0 + tx;
+      if (t >= T || k >= NF) continue;
+      float vr = tr[tx][r], vi = ti[tx][r];
+      const int64_t o = (((int64_t)b * T + t) * NS + k + 1) * 2;
+      if (d.mode == 3) {                                     // (g_mags, g_phase) -> (d re, d im); m == 0: 0, where the reference has NaN
+        const float re = spec[o], im = spec[o + 1], m = sqrtf(re * re + im * im);
+        const float gm = vr, gp = vi;
+        vr = m == 0.f ? 0.f : gm * re / m - gp * (im / m) / m;
+        vi = m == 0.f ? 0.f : gm * im / m + gp * (re / m) / m;
+      }
+      dst[o] = vr; dst[o + 1] = vi;
+      if (k == 0) { dst[o - 2] = 0.f; dst[o - 1] = 0.f; }     // slot 0
+    }
+  }
+}
+
 void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st) {
   const int64_t frames = (int64_t)d.B * d.T;
   if (!d.pair) { hipLaunchKernelGGL(stft_fft_single_kernel, dim3((unsigned)((frames + 4 * kStftFPW - 1) / (4 * kStftFPW))), dim3(256), 0, st, d, ab); return; }
@@ -328,6 +477,14 @@ void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st) {
 }
 void launch_istft_fft(const IstftFft& d, const ArenaBases& ab, hipStream_t st) {
   hipLaunchKernelGGL(istft_fft_kernel, dim3((unsigned)((d.nframes + 3) / 4)), dim3(256), 0, st, d, ab);
+}
+void launch_ifft_ola(const IfftOla& d, const ArenaBases& ab, hipStream_t st) {
+  const int runs = (d.T + d.fpw - 1) / d.fpw;
+  const size_t stage = (size_t)(d.halo + d.fpw) * d.W * sizeof(float);
+  hipLaunchKernelGGL(ifft_ola_kernel, dim3((unsigned)(d.B * runs)), dim3(256), stage, st, d, ab);
+}
+void launch_specconv(const SpecConv& d, const ArenaBases& ab, hipStream_t st) {
+  hipLaunchKernelGGL(specconv_kernel, dim3((d.T + 31) / 32, (d.NF + 31) / 32, d.B), dim3(256), 0, st, d, ab);
 }
 
 }  // namespace sefd

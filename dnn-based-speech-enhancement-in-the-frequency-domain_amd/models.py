@@ -20,26 +20,126 @@ from . import tools_for_loss as tfl
 
 
 # ------------------------------------------------------------------------------------------ parameter holders
-class ConvSTFT(nn.Module):
-    """Buffer holder for `stft.weight` (tools_for_model.py:36-52)."""
+def _default_fft_len(win_len):
+    # tools_for_model.py:41-42: np.int(2 ** np.ceil(np.log2(win_len))) - `np.int` no longer exists in numpy; this is the value it meant
+    return 1 << max(int(win_len) - 1, 0).bit_length()
 
-    def __init__(self, win_len, win_inc, fft_len, win_type, feature_type='complex', fix=True):
+
+def _frontend_runtime(mod, model, B, n, device, complex_io):
+    """(plan, arenas) of a ConvSTFT / ConviSTFT module at batch B and n = clip length L / frame count T, cached on the module."""
+    key = (model, B, n, str(device), complex_io)
+    rt = mod._runtimes.get(key)
+    if rt is None:
+        plan = Plan(B, n, win_len=mod.win_len, win_inc=mod.stride, fft_len=mod.dim, model=model, win_type=mod.win_type,
+                    feature_type="complex" if complex_io else "real")
+        rt = (plan, plan.alloc_arenas(device))
+        mod._runtimes[key] = rt
+    return rt
+
+
+def _check_frontend_input(name, *tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"sefd {name} runs on the MI355X only (inputs must be a cuda tensor); there is no CPU fallback")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"sefd {name} is built for float32 only, got {t.dtype}")
+
+
+class _FrontendFunction(torch.autograd.Function):
+    """One ConvSTFT / ConviSTFT plan (csrc/plan_frontend.cpp) at its IO boundary: `ins` / `outs` / `gouts` / `gins` are lists of
+    (IO buffer name, shape).  `keep` names the plan buffers the backward phase reads besides the cotangents (the spectrum under (mags, phase),
+    the polar inputs): they are cloned when an input requires grad and put back before the backward phase, so any number of forwards of one
+    shape may precede their backwards.  The backward phase runs only when autograd asks for it; double backward is not supported."""
+
+    @staticmethod
+    def forward(ctx, rt, ins, outs, gouts, gins, keep, *tensors):
+        plan, ar = rt
+        for (name, shape), t in zip(ins, tensors):
+            plan.io(ar, name, shape).copy_(t.reshape(shape))
+        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
+        ctx.rt, ctx.gouts, ctx.gins, ctx.keep = rt, gouts, gins, keep
+        ctx.in_shapes = [t.shape for t in tensors]
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(*[plan.view(ar, name).clone() for name in keep])
+        res = tuple(plan.io(ar, name, shape).clone() for name, shape in outs)
+        return res if len(res) > 1 else res[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        plan, ar = ctx.rt
+        for name, t in zip(ctx.keep, ctx.saved_tensors):
+            plan.view(ar, name).copy_(t)
+        for (name, shape), g in zip(ctx.gouts, grads):
+            plan.io(ar, name, shape).copy_(g.reshape(shape))
+        plan.run(PHASE_BWD, ar, torch.cuda.current_stream().cuda_stream)
+        return (None,) * 6 + tuple(plan.io(ar, name, shape).clone().reshape(ish) for (name, shape), ish in zip(ctx.gins, ctx.in_shapes))
+
+
+class ConvSTFT(nn.Module):
+    """tools_for_model.py:36-68, same constructor, buffer (`weight`) and forward: [B, L] or [B, 1, L] -> [B, 2 NF, T] ('complex': real block, then
+    imaginary block) or (mags, phase), each [B, NF, T].  Differentiable in the waveform; computed by the ConvSTFT plan (csrc/plan_frontend.cpp).
+    Where a bin's magnitude is exactly 0 the gradient of (mags, phase) is 0 (the reference: NaN).  float32 cuda tensors only."""
+
+    def __init__(self, win_len, win_inc, fft_len=None, win_type='hamming', feature_type='real', fix=True):
         super().__init__()
+        fft_len = _default_fft_len(win_len) if fft_len is None else fft_len
         K, _, _ = stft_kernels(win_len, fft_len, win_type)
         self.register_buffer('weight', K)
         self.feature_type, self.stride, self.win_len, self.dim = feature_type, win_inc, win_len, fft_len
+        self.fft_len, self.win_type = fft_len, win_type
+        self._runtimes = {}
+
+    def forward(self, inputs):
+        _check_frontend_input("ConvSTFT", inputs)
+        if inputs.dim() not in (2, 3) or (inputs.dim() == 3 and inputs.shape[1] != 1):
+            raise ValueError(f"ConvSTFT takes [B, L] or [B, 1, L], got {tuple(inputs.shape)}")
+        B, L = inputs.shape[0], inputs.shape[-1]
+        rt = _frontend_runtime(self, "ConvSTFT", B, L, inputs.device, self.feature_type == 'complex')
+        NF, T = rt[0].NF, rt[0].T
+        if self.feature_type == 'complex':
+            outs, gouts = [("out", (B, 2 * NF, T))], [("grad_out", (B, 2 * NF, T))]
+        else:
+            outs = [("mags", (B, NF, T)), ("phase", (B, NF, T))]
+            gouts = [("grad_mags", (B, NF, T)), ("grad_phase", (B, NF, T))]
+        keep = [] if self.feature_type == 'complex' else ["spec"]
+        return _FrontendFunction.apply(rt, [("wav", (B, L))], outs, gouts, [("grad_wav", (B, L))], keep, inputs)
 
 
 class ConviSTFT(nn.Module):
-    """Buffer holder for `istft.weight/window/enframe` (tools_for_model.py:71-88)."""
+    """tools_for_model.py:71-112, same constructor, buffers (`weight`, `window`, `enframe`) and forward: [B, 2 NF, T], or mags [B, NF, T] with
+    `phase`, -> [B, 1, (T - 1) hop + win_len - 2 (win_len - hop)].  No clamp; the overlap-add is divided by coff + 1e-8.  Differentiable in
+    `inputs` and `phase`; computed by the ConviSTFT plan (csrc/plan_frontend.cpp).  float32 cuda tensors only."""
 
-    def __init__(self, win_len, win_inc, fft_len, win_type, feature_type='complex', fix=True):
+    def __init__(self, win_len, win_inc, fft_len=None, win_type='hamming', feature_type='real', fix=True):
         super().__init__()
+        fft_len = _default_fft_len(win_len) if fft_len is None else fft_len
         _, Kinv, w = stft_kernels(win_len, fft_len, win_type)
         self.register_buffer('weight', Kinv)
         self.register_buffer('window', w)
         self.register_buffer('enframe', torch.eye(win_len)[:, None, :])
         self.feature_type, self.stride, self.win_len, self.dim = feature_type, win_inc, win_len, fft_len
+        self.fft_len, self.win_type = fft_len, win_type
+        self._runtimes = {}
+
+    def forward(self, inputs, phase=None):
+        _check_frontend_input("ConviSTFT", *([inputs] if phase is None else [inputs, phase]))
+        NF = self.dim // 2 + 1
+        want = NF if phase is not None else 2 * NF
+        if inputs.dim() != 3 or inputs.shape[1] != want or (phase is not None and phase.shape != inputs.shape):
+            raise ValueError(f"ConviSTFT takes [B, {2 * NF}, T], or mags and phase [B, {NF}, T] each; got {tuple(inputs.shape)}"
+                             + ("" if phase is None else f" and {tuple(phase.shape)}"))
+        B, T = inputs.shape[0], inputs.shape[2]
+        # the input form decides the plan, not feature_type: the reference's forward looks at `phase` alone (tools_for_model.py:96-99)
+        rt = _frontend_runtime(self, "ConviSTFT", B, T, inputs.device, phase is None)
+        Lout = (T - 1) * self.stride + self.win_len - 2 * (self.win_len - self.stride)
+        if phase is None:
+            ins, gins, args, keep = [("in", (B, 2 * NF, T))], [("grad_in", (B, 2 * NF, T))], (inputs,), []
+        else:
+            ins = [("mags", (B, NF, T)), ("phase", (B, NF, T))]
+            gins, args, keep = [("grad_mags", (B, NF, T)), ("grad_phase", (B, NF, T))], (inputs, phase), ["io.mags", "io.phase"]
+        wav = _FrontendFunction.apply(rt, ins, [("wav", (B, Lout))], [("grad_wav", (B, Lout))], gins, keep, *args)
+        return wav.unsqueeze(1)
 
 
 class ComplexConv2d(nn.Module):

@@ -21,12 +21,13 @@ class Plan:
     def __init__(self, B, L, kernel_num=(32, 64, 128, 256, 256, 256), rnn_layers=2, rnn_units=256, win_len=400,
                  win_inc=100, fft_len=512, masking_mode="E", lstm="complex", skip_type=True, act_dtype="fp32",
                  kernel_size=5, training=True, model="DCCRN", fsn=None, bn_world=1, grad_buckets=1, use_cbn=False, win_type="hanning",
-                 cbn_sync=False, seq=None):
+                 cbn_sync=False, seq=None, feature_type="complex"):
         self.lib = _lib.lib()
         if masking_mode not in MASK_MODES:
             raise NotImplementedError(f"masking_mode {masking_mode!r} is not on the HIP path yet")
         cfg = _lib.ModelConfig()
-        cfg.model = {"DCCRN": 0, "CRN": 1, "STFT": 2, "FullSubNet": 3, "TorchSTFT": 4, "TorchISTFT": 5, "SequenceModel": 6}[model]
+        cfg.model = {"DCCRN": 0, "CRN": 1, "STFT": 2, "FullSubNet": 3, "TorchSTFT": 4, "TorchISTFT": 5, "SequenceModel": 6, "ConvSTFT": 7,
+                     "ConviSTFT": 8}[model]
         cfg.B, cfg.L = int(B), int(L)
         if model == "FullSubNet":
             # L = number of STFT frames T; kernel_num carries (sb_neighbors, fb_neighbors, look_ahead, fb_hidden, sb_hidden,
@@ -48,8 +49,12 @@ class Plan:
             kernel_num = (s["input_size"], s["output_size"], s["hidden_size"], s["num_layers"], 1 if s["bidirectional"] else 0,
                           {"LSTM": 0, "GRU": 1}[s["sequence_model"]], int(round(s["keep"] * 1000)))
             self.seq = s
+        if model in ("ConvSTFT", "ConviSTFT"):
+            # the modules on their own (csrc/plan_frontend.cpp): kernel_num[0] = feature type, 0 'complex', 1 anything else (mags, phase);
+            # ConviSTFT: L = frames T
+            kernel_num = (0 if feature_type == "complex" else 1,)
         cfg.win_len, cfg.hop, cfg.fft_len = win_len, win_inc, fft_len
-        cfg.n_layers = len(kernel_num) if model not in ("FullSubNet", "SequenceModel") else 0
+        cfg.n_layers = len(kernel_num) if model not in ("FullSubNet", "SequenceModel", "ConvSTFT", "ConviSTFT") else 0
         for i, k in enumerate(kernel_num):
             cfg.kernel_num[i] = int(k)
         cfg.rnn_layers, cfg.rnn_units = rnn_layers, rnn_units

@@ -15,9 +15,19 @@ def __getattr__(name):
     if name == "SequenceModel":
         from .models import SequenceModel
         return SequenceModel
+    if name in ("ConvSTFT", "ConviSTFT"):                  # tools_for_model.py:36-112, defined in models.py beside the models that hold them
+        from . import models
+        return getattr(models, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 _FE_CACHE = {}
+
+
+def init_kernels(win_len, win_inc, fft_len, win_type=None, invers=False):
+    """tools_for_model.py:16-33: (kernel [2 NF, 1, win_len], window [1, win_len, 1]) of ConvSTFT (invers=False) / ConviSTFT (invers=True)."""
+    from .frontend_consts import stft_kernels
+    K, Kinv, w = stft_kernels(win_len, fft_len, win_type)
+    return (Kinv if invers else K), w
 
 
 def _vp(t):

@@ -24,15 +24,22 @@ typedef struct sefd_plan sefd_plan;
 /* Mirror of the config.py knobs that shape DCCRN (config.py:35-68) plus batch geometry. */
 typedef struct sefd_model_config {
   int32_t model;          /* 0 DCCRN, 1 CRN, 2 ConvSTFT front end, 3 FullSubNet, 4 torch.stft front end, 5 torch.istft,
-                             6 SequenceModel on its own (see build_plan, csrc/plan.cpp) */
-  int32_t B, L;           /* batch, samples per clip */
+                             6 SequenceModel on its own, 7 ConvSTFT on its own, 8 ConviSTFT on its own (see build_plan, csrc/plan.cpp) */
+  int32_t B, L;           /* batch, samples per clip (models 3, 6 and 8: L = frames T) */
   int32_t win_len, hop, fft_len;
   int32_t n_layers;
   int32_t kernel_num[12]; /* cfg.dccrn_kernel_num; FullSubNet (model 3): sb/fb neighbours (each 0 .. 31), look_ahead, fb/sb hidden,
                              fb/sb output activation (0 None, 1 ReLU, 2 Tanh, 3 ReLU6), dropout keep in 1/1000, [8] sequence model (0 LSTM, 1 GRU), [9] norm type (0 offline_laplace_norm,
                              1 cumulative_laplace_norm, 2 offline_gaussian_norm, 3 cumulative_layer_norm);
                              SequenceModel (model 6; B = sequences, L = frames T): input size, output size, hidden size (multiple of 8), num_layers (1 .. 8), bidirectional,
-                             sequence model (0 LSTM, 1 GRU), dropout keep in 1/1000.  I/O, time-major fp32: x [T][B][roundup(I, 8)] -> y [T][B][O]; grad_y -> grad_x */
+                             sequence model (0 LSTM, 1 GRU), dropout keep in 1/1000.  I/O, time-major fp32: x [T][B][roundup(I, 8)] -> y [T][B][O]; grad_y -> grad_x;
+                             ConvSTFT / ConviSTFT (models 7 / 8, tools_for_model.py:36-112; fp32, NF = fft_len / 2 + 1, window / window_values as for DCCRN): [0] = feature type,
+                             0 'complex' (one [B][2 NF][T] tensor, real block then imaginary block), 1 anything else ((mags, phase), [B][NF][T] each).
+                             Model 7, T = (L + 2 (win_len - hop) - win_len) / hop + 1: forward wav [B][L] -> out | mags, phase; backward grad_out | grad_mags, grad_phase -> grad_wav
+                             (where a bin's magnitude is exactly 0 its (mags, phase) gradient is 0; the reference has NaN there).
+                             Model 8, L = T, Lout = (T - 1) hop + win_len - 2 (win_len - hop): forward in | mags, phase -> wav [B][Lout] (no clamp, overlap-add / (coff + 1e-8));
+                             backward grad_wav -> grad_in | grad_mags, grad_phase.  Refused, one sentence each: T < 1, Lout <= 0, win_len > fft_len, hop outside 1 .. win_len.
+                             fft_len 512 runs the FFT kernels, any other even fft_len the framing / synthesis GEMMs and their transposes */
   int32_t rnn_layers, rnn_units;
   int32_t mask_mode;      /* 0 'E', 1 'C', 2 'R' (cfg.masking_mode) */
   int32_t lstm_complex;   /* cfg.lstm == 'complex' */
