@@ -136,6 +136,10 @@ int32_t sefd_plan_op_info(const sefd_plan* h, int phase, int i, int64_t* o) {
     o[7] = (int64_t)f.B * f.T * 258 * 8 + (int64_t)f.B * f.Lout * 4;
   } else if (op.kind == OP_SPECCONV) {
     o[2] = (int64_t)op.sc.B * op.sc.T; o[3] = op.sc.NF; o[5] = (int64_t)op.sc.mode << 8;
+  } else if (op.kind == OP_NCHW_CL) {                                      // HBM-bound: the fp32 tensor on one side, the padded channels-last one on the other
+    const NchwCl& l = op.lay;
+    o[2] = (int64_t)l.B * l.F * l.T; o[3] = l.C; o[5] = l.dt | ((int64_t)l.mode << 8);
+    o[7] = (int64_t)l.B * l.F * l.T * ((int64_t)l.C * 4 + (int64_t)l.Cpad * esize(l.dt));
   }
   return 0;
 }
@@ -708,6 +712,24 @@ int32_t sefd_adam_step_guarded_dp(float* param, const float* grad, float* exp_av
   int grid = (int)((n + 255) / 256); if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n, (float)(lr / bc1), (float)std::sqrt(bc2),
                      beta1, beta2, eps, grad_scale, skip_if_set, skip_if_nan);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+// One launch of the layout kernel (layout.hip, struct NchwCl) on raw device pointers: nchw fp32 [B][C][F][T], cl (dt 0 fp32, 1 bf16) [B][Tcl][F][Cpad],
+// nchw frame t = cl frame t + t_off; mode 0 / 2: nchw -> cl, 1 / 3: cl -> nchw.  Tests and tools/convlayers_bench.py; plans reach the kernel as OP_NCHW_CL.
+int32_t sefd_nchw_cl(void* nchw, void* cl, int32_t B, int32_t C, int32_t Cpad, int32_t F, int32_t T, int32_t Tcl, int32_t t_off, int32_t dt, int32_t mode,
+                     void* stream) {
+  if (!nchw || !cl || B < 1 || C < 1 || F < 1 || T < 1 || F > 65535 || Cpad < C || Cpad % 8 || t_off < 0 || (int64_t)T + t_off > Tcl || dt < 0 || dt > 1 ||
+      mode < 0 || mode > 3)
+    return -1;
+  sefd::ArenaBases ab;
+  std::memset(&ab, 0, sizeof(ab));
+  ab.p[sefd::A_IO] = static_cast<char*>(nchw);
+  ab.p[sefd::A_WS] = static_cast<char*>(cl);
+  sefd::NchwCl d;
+  std::memset(&d, 0, sizeof(d));
+  d.nchw.arena = sefd::A_IO; d.cl.arena = sefd::A_WS;
+  d.B = B; d.C = C; d.Cpad = Cpad; d.F = F; d.T = T; d.Tcl = Tcl; d.t_off = t_off; d.dt = dt; d.mode = mode;
+  sefd::launch_nchw_cl(d, ab, static_cast<hipStream_t>(stream));
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 void sefd_tuning_set(const char* knob, const char* value) { if (knob) sefd::tune_set(knob, value); }

@@ -9,7 +9,7 @@
 namespace sefd {
 
 struct ModelConfig {
-  int32_t model;            // 0 = DCCRN, 1 = CRN, ... 6 = SequenceModel, 7 = ConvSTFT, 8 = ConviSTFT (include/sefd.h sefd_model_config; build_plan)
+  int32_t model;            // 0 = DCCRN, 1 = CRN, ... 6 = SequenceModel, 7 = ConvSTFT, 8 = ConviSTFT, 9 = ConvLayer, 10 = ComplexBatchNorm (include/sefd.h sefd_model_config; build_plan)
   int32_t B, L;
   int32_t win_len, hop, fft_len;
   int32_t n_layers;

@@ -939,5 +939,7 @@ Plan* build_torchstft_plan(const ModelConfig& cfg);
 Plan* build_torchistft_plan(const ModelConfig& cfg);
 Plan* build_convstft_plan(const ModelConfig& cfg);
 Plan* build_convistft_plan(const ModelConfig& cfg);
+Plan* build_convlayer_plan(const ModelConfig& cfg);
+Plan* build_cbn_plan(const ModelConfig& cfg);
 
 }  // namespace sefd

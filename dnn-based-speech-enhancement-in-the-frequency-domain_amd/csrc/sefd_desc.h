@@ -374,6 +374,16 @@ struct SpecConv {
   Ptr spec, a, b, dspec, ga, gb;
   int32_t B, T, NF, mode;
 };
+// Reference layout <-> channels-last at the boundary of a layer that runs on its own (ComplexConv2d ... ComplexBatchNorm as modules, plan_layers.cpp;
+// layout.hip): nchw fp32 [B][C][F][T] against cl (dtype dt) [B][Tcl][F][Cpad], frame t of nchw = frame t + t_off of cl.  32 x 32 tiles over
+// (channel, frame) of one (b, f), transposed through LDS: the nchw side moves runs of frames, the cl side runs of channels.
+//   mode 0 input in, 2 cotangent in: nchw -> cl, channels C .. Cpad - 1 written as zero, cl frames outside [t_off, t_off + T) untouched
+//   mode 1 output out, 3 input gradient out: cl -> nchw, pad channels dropped
+struct NchwCl {
+  Ptr nchw, cl;
+  int32_t B, C, Cpad, F, T, Tcl, t_off, dt;
+  int32_t mode, pad_;
+};
 // torch.stft(center=True, pad_mode='reflect'): dst[b][i] = src[b][reflect(i - pad)], i < L + 2*pad
 struct ReflectPad {
   Ptr src, dst;
@@ -469,6 +479,7 @@ enum OpKind : int32_t {
   OP_FSN_ACT,                        // Tanh / ReLU6 of FullSubNet's full-band head (struct Fsn)
   OP_IFFT_OLA,                       // fused inverse FFT + window + overlap-add (struct IfftOla)
   OP_SPECCONV,                       // ConvSTFT / ConviSTFT spectrum conversions (struct SpecConv)
+  OP_NCHW_CL,                        // reference layout <-> channels-last at a stand-alone layer's boundary (struct NchwCl)
 };
 
 constexpr int kOpHold = 2;     // Op::join of a lane-1 op
@@ -510,6 +521,7 @@ struct Op {
     CbnBwd cbb;
     IfftOla iola;
     SpecConv sc;
+    NchwCl lay;
   };
 };
 

@@ -142,55 +142,7 @@ class ConviSTFT(nn.Module):
         return wav.unsqueeze(1)
 
 
-class ComplexConv2d(nn.Module):
-    """Parameter holder with the reference's layout and init (tools_for_model.py:199-241)."""
-
-    def __init__(self, in_channels, out_channels, kernel_size, stride, padding):
-        super().__init__()
-        self.real_conv = nn.Conv2d(in_channels // 2, out_channels // 2, kernel_size, stride, padding=[padding[0], 0])
-        self.imag_conv = nn.Conv2d(in_channels // 2, out_channels // 2, kernel_size, stride, padding=[padding[0], 0])
-        for c in (self.real_conv, self.imag_conv):
-            nn.init.normal_(c.weight.data, std=0.05)
-            nn.init.constant_(c.bias, 0.)
-
-
-class ComplexConvTranspose2d(nn.Module):
-    """Parameter holder (tools_for_model.py:272-309)."""
-
-    def __init__(self, in_channels, out_channels, kernel_size, stride, padding, output_padding):
-        super().__init__()
-        self.real_conv = nn.ConvTranspose2d(in_channels // 2, out_channels // 2, kernel_size, stride, padding=padding,
-                                            output_padding=output_padding)
-        self.imag_conv = nn.ConvTranspose2d(in_channels // 2, out_channels // 2, kernel_size, stride, padding=padding,
-                                            output_padding=output_padding)
-        for c in (self.real_conv, self.imag_conv):
-            nn.init.normal_(c.weight.data, std=0.05)
-            nn.init.constant_(c.bias, 0.)
-
-
-class ComplexBatchNorm(nn.Module):
-    """Parameter / buffer holder of the reference's ComplexBatchNorm (tools_for_model.py:430-480): Wrr, Wri, Wii, Br, Bi and the running
-    RMr, RMi, RVrr, RVri, RVii over num_features // 2 complex channels; `reset_parameters` as there (Wri ~ U(-0.9, 0.9)).  The arithmetic is
-    csrc/cbn.hip."""
-
-    def __init__(self, num_features, eps=1e-5, momentum=0.1):
-        super().__init__()
-        self.num_features, self.eps, self.momentum = num_features // 2, eps, momentum
-        h = self.num_features
-        for name in ("Wrr", "Wri", "Wii", "Br", "Bi"):
-            setattr(self, name, nn.Parameter(torch.empty(h)))
-        self.register_buffer("RMr", torch.zeros(h))
-        self.register_buffer("RMi", torch.zeros(h))
-        self.register_buffer("RVrr", torch.ones(h))
-        self.register_buffer("RVri", torch.zeros(h))
-        self.register_buffer("RVii", torch.ones(h))
-        self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
-        with torch.no_grad():
-            self.Br.zero_()
-            self.Bi.zero_()
-            self.Wrr.fill_(1)
-            self.Wri.uniform_(-.9, +.9)
-            self.Wii.fill_(1)
+# (ComplexConv2d, ComplexConvTranspose2d, ComplexBatchNorm: below, on _SefdModule)
 
 
 class NavieComplexLSTM(nn.Module):
@@ -289,7 +241,7 @@ class _SefdModule(nn.Module):
         return [(n, p) for n, p in self.named_parameters()]
 
     def _bn_buffers(self):
-        return [(n, b) for n, b in self.named_buffers() if n.endswith(("running_mean", "running_var", ".RMr", ".RMi", ".RVrr", ".RVri", ".RVii"))]
+        return [(n, b) for n, b in self.named_buffers() if n.rsplit(".", 1)[-1] in ("running_mean", "running_var", "RMr", "RMi", "RVrr", "RVri", "RVii")]
 
     def _flat_ok(self, device):
         fp = self._flat_param
@@ -321,14 +273,14 @@ class _SefdModule(nn.Module):
         for name, b in bs:
             n = b.numel()
             st[off:off + n].copy_(b.reshape(-1).to(device=device, dtype=torch.float32))
-            mname, leaf = name.rsplit(".", 1)
+            mname, leaf = name.rsplit(".", 1) if "." in name else ("", name)         # '': the module itself (a layer on its own)
             mods[mname]._buffers[leaf] = st[off:off + n].view(b.shape)
             off += n
         nbts = [(n, b) for n, b in self.named_buffers() if n.endswith("num_batches_tracked")]
         nbt = torch.zeros(len(nbts), dtype=torch.long, device=device)
         for i, (name, b) in enumerate(nbts):
             nbt[i] = b.to(device)
-            mname, leaf = name.rsplit(".", 1)
+            mname, leaf = name.rsplit(".", 1) if "." in name else ("", name)
             mods[mname]._buffers[leaf] = nbt[i]
         self._flat_param, self._flat_state, self._flat_nbt = flat, st, nbt
         self._flat_grad = torch.zeros_like(flat)
@@ -513,6 +465,284 @@ def _dp_guard_tick(model):
         _check_dp_guard(model)
 
 
+# ------------------------------------------------------------------------------------------ the layers of tools_for_model.py:126-607
+class _LayerFunction(torch.autograd.Function):
+    """One ConvLayer / ComplexBatchNorm plan (csrc/plan_layers.cpp) at its reference-layout boundary: io.x -> io.y, io.grad_y -> io.grad_x and the flat
+    gradient arena.  The saved activations live in the runtime's workspace: a later forward of the same shape invalidates this one's backward (stamp)."""
+
+    @staticmethod
+    def forward(ctx, owner, rt, x, out_shape, *params):
+        plan, ar = rt
+        plan.io(ar, "x", tuple(x.shape)).copy_(x)
+        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
+        plan.stamp = getattr(plan, "stamp", 0) + 1
+        ctx.owner, ctx.rt, ctx.in_shape, ctx.out_shape, ctx.stamp = owner, rt, tuple(x.shape), out_shape, plan.stamp
+        return plan.io(ar, "y", out_shape).clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        plan, ar = ctx.rt
+        if ctx.stamp != plan.stamp:
+            raise RuntimeError("sefd: a later forward of the same shape overwrote the activations this backward needs")
+        plan.io(ar, "grad_y", ctx.out_shape).copy_(g)
+        plan.run(PHASE_BWD, ar, torch.cuda.current_stream().cuda_stream)
+        flat = ctx.owner._flat_grad.clone()
+        return (None, None, plan.io(ar, "grad_x", ctx.in_shape).clone(), None) + tuple(
+            flat[off:off + n].view(shape) for (off, n, shape) in ctx.owner._param_slices)
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+class _ConvLayer(_SefdModule):
+    """What the four conv layers share: the accepted domain (refusals at construction), the plan of a (B, F, T) and `forward`.  As children of
+    DCCRN / CRN they are parameter holders: the parent owns the flat arenas and plans the whole conv stack itself."""
+
+    _KIND = None          # plan.CONV_KINDS name
+    _COMPLEX = False
+
+    def _setup(self, in_channels, out_channels, kernel_size, stride, padding, dilation, groups, complex_axis, output_padding):
+        name = self._KIND
+        k, s, p, op = _pair(kernel_size), _pair(stride), _pair(padding), _pair(output_padding)
+        if _pair(dilation) != (1, 1):
+            raise NotImplementedError(f"sefd {name}: dilation {dilation} is not built (1 only)")
+        if groups != 1:
+            raise NotImplementedError(f"sefd {name}: groups {groups} is not built (1 only)")
+        if complex_axis != 1:
+            raise NotImplementedError(f"sefd {name}: complex_axis {complex_axis} is not built (the channel axis, 1, only)")
+        if s[1] != 1:
+            raise NotImplementedError(f"sefd {name}: a time stride of {s[1]} is not built (1 only)")
+        if not 1 <= s[0] <= 2:
+            raise NotImplementedError(f"sefd {name}: a frequency stride of {s[0]} is not built (1 .. 2)")
+        if not 1 <= k[0] <= 7:
+            raise NotImplementedError(f"sefd {name}: a kernel of {k[0]} bins is not built (1 .. 7)")
+        if not 1 <= k[1] <= 4:
+            raise NotImplementedError(f"sefd {name}: a kernel of {k[1]} frames is not built (1 .. 4: a launch descriptor holds 8 runs over two sources)")
+        if not (0 <= p[0] < k[0] and 0 <= p[1] < k[1]):
+            raise NotImplementedError(f"sefd {name}: padding {tuple(p)} must stay below the kernel extent {tuple(k)}")
+        if not (0 <= op[0] < s[0] and 0 <= op[1] < s[1]):
+            raise NotImplementedError(f"sefd {name}: output padding {tuple(op)} must stay below the stride {tuple(s)}")
+        if self._COMPLEX and (in_channels % 2 or out_channels % 2):
+            raise NotImplementedError(f"sefd {name}: odd channel counts ({in_channels} -> {out_channels}) have no real / imaginary halves")
+        self._geo = dict(kind=name, in_channels=int(in_channels), out_channels=int(out_channels), kernel_size=k, stride_f=int(s[0]), padding=p,
+                         output_padding_f=int(op[0]))
+        self.act_dtype = cfg.act_dtype
+
+    def _layer_runtime(self, B, F, T, device):
+        if not self._flat_ok(device):
+            self._flatten(device)
+        key = ("conv", B, F, T, self.act_dtype, str(device))
+        rt = self._runtimes.get(key)
+        if rt is None:
+            plan = Plan(B, T, act_dtype=self.act_dtype, training=True, model="ConvLayer",
+                        conv=dict(self._geo, causal=bool(getattr(self, "causal", True)), F=F))
+            rt = _layer_arenas(self, plan, device)
+            self._runtimes[key] = rt
+        return rt
+
+    def forward(self, inputs):
+        name, g = self._KIND, self._geo
+        if isinstance(inputs, (tuple, list)) and name == "ComplexConvTranspose2d":          # the reference's (real, imag) form, tools_for_model.py:315-317
+            inputs = torch.cat([inputs[0], inputs[1]], 1)
+        _check_frontend_input(name, inputs)
+        if inputs.dim() != 4 or inputs.shape[1] != g["in_channels"]:
+            raise ValueError(f"{name} takes [B, {g['in_channels']}, F, T], got {tuple(inputs.shape)}")
+        B, _, F, T = inputs.shape
+        plan, ar = rt = self._layer_runtime(B, F, T, inputs.device)
+        k, p = g["kernel_size"], g["padding"]
+        if "Transpose" in name:
+            Fo = (F - 1) * g["stride_f"] - 2 * p[0] + k[0] + g["output_padding_f"]
+        else:
+            Fo = (F + 2 * p[0] - k[0]) // g["stride_f"] + 1
+        return _LayerFunction.apply(self, rt, inputs.contiguous(), (B, g["out_channels"], Fo, plan.T), *[q for _, q in self._trainable()])
+
+
+def _layer_arenas(owner, plan, device):
+    """(plan, arenas) of a layer that owns its flat parameters; the plan's parameter table must agree with the module (names, order, offsets)."""
+    plan.owner = weakref.ref(owner)
+    assert [n for n, _ in owner._trainable()] == list(plan.params.keys()), "parameter order differs from the plan"
+    assert [s[0] for s in owner._param_slices] == [v[0] for v in plan.params.values()]
+    ar = [None] * ARENA_COUNT
+    ar[ARENA_WS] = torch.zeros(max(plan.arena_bytes[ARENA_WS], 256), dtype=torch.uint8, device=device)
+    ar[ARENA_CONST] = torch.from_numpy(plan.const_image()).to(device)
+    ar[ARENA_IO] = torch.zeros(plan.arena_bytes[ARENA_IO], dtype=torch.uint8, device=device)
+    ar[ARENA_PARAM], ar[ARENA_GRAD], ar[ARENA_STATE] = owner._flat_param, owner._flat_grad, owner._flat_state
+    return plan, ar
+
+
+def _init_conv(*convs):
+    for c in convs:
+        nn.init.normal_(c.weight.data, std=0.05)
+        nn.init.constant_(c.bias, 0.)
+
+
+class ComplexConv2d(_ConvLayer):
+    """tools_for_model.py:199-269, same constructor, attributes, parameters (`real_conv`, `imag_conv`) and init; forward [B, C, F, T] ->
+    [B, C_out, F_out, T_out] (real half, then imaginary half of the channels), differentiable in the input and the parameters (ConvLayer plan,
+    csrc/plan_layers.cpp).  causal: the time padding goes to the left only.  float32 cuda tensors."""
+    _KIND, _COMPLEX = "ComplexConv2d", True
+
+    def __init__(self, in_channels, out_channels, kernel_size=(1, 1), stride=(1, 1), padding=(0, 0), dilation=1, groups=1, causal=True,
+                 complex_axis=1):
+        super().__init__()
+        self._setup(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, complex_axis, (0, 0))
+        self.in_channels, self.out_channels = in_channels // 2, out_channels // 2
+        self.kernel_size, self.stride, self.padding, self.causal = kernel_size, stride, padding, causal
+        self.groups, self.dilation, self.complex_axis = groups, dilation, complex_axis
+        self.real_conv = nn.Conv2d(self.in_channels, self.out_channels, kernel_size, stride, padding=[padding[0], 0], dilation=dilation, groups=groups)
+        self.imag_conv = nn.Conv2d(self.in_channels, self.out_channels, kernel_size, stride, padding=[padding[0], 0], dilation=dilation, groups=groups)
+        _init_conv(self.real_conv, self.imag_conv)
+        self._init_runtime_state()
+
+
+class ComplexConvTranspose2d(_ConvLayer):
+    """tools_for_model.py:272-338; `forward` also takes the reference's (real, imag) tuple or list."""
+    _KIND, _COMPLEX = "ComplexConvTranspose2d", True
+
+    def __init__(self, in_channels, out_channels, kernel_size=(1, 1), stride=(1, 1), padding=(0, 0), output_padding=(0, 0), causal=False,
+                 complex_axis=1, groups=1):
+        super().__init__()
+        self._setup(in_channels, out_channels, kernel_size, stride, padding, 1, groups, complex_axis, output_padding)
+        self.in_channels, self.out_channels = in_channels // 2, out_channels // 2
+        self.kernel_size, self.stride, self.padding, self.output_padding, self.groups = kernel_size, stride, padding, output_padding, groups
+        self.real_conv = nn.ConvTranspose2d(self.in_channels, self.out_channels, kernel_size, stride, padding=padding, output_padding=output_padding,
+                                            groups=groups)
+        self.imag_conv = nn.ConvTranspose2d(self.in_channels, self.out_channels, kernel_size, stride, padding=padding, output_padding=output_padding,
+                                            groups=groups)
+        self.complex_axis = complex_axis
+        _init_conv(self.real_conv, self.imag_conv)
+        self._init_runtime_state()
+
+
+class RealConv2d(_ConvLayer):
+    """tools_for_model.py:341-388."""
+    _KIND = "RealConv2d"
+
+    def __init__(self, in_channels, out_channels, kernel_size=(1, 1), stride=(1, 1), padding=(0, 0), dilation=1, groups=1, causal=True,
+                 complex_axis=1):
+        super().__init__()
+        self._setup(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, complex_axis, (0, 0))
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.stride, self.padding, self.causal = kernel_size, stride, padding, causal
+        self.groups, self.dilation = groups, dilation
+        self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding=[padding[0], 0], dilation=dilation, groups=groups)
+        _init_conv(self.conv)
+        self._init_runtime_state()
+
+
+class RealConvTranspose2d(_ConvLayer):
+    """tools_for_model.py:391-425."""
+    _KIND = "RealConvTranspose2d"
+
+    def __init__(self, in_channels, out_channels, kernel_size=(1, 1), stride=(1, 1), padding=(0, 0), output_padding=(0, 0), groups=1):
+        super().__init__()
+        self._setup(in_channels, out_channels, kernel_size, stride, padding, 1, groups, 1, output_padding)
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.kernel_size, self.stride, self.padding, self.output_padding, self.groups = kernel_size, stride, padding, output_padding, groups
+        self.conv = nn.ConvTranspose2d(in_channels, out_channels, kernel_size, stride, padding=padding, output_padding=output_padding, groups=groups)
+        _init_conv(self.conv)
+        self._init_runtime_state()
+
+
+class ComplexBatchNorm(_SefdModule):
+    """tools_for_model.py:430-607, same constructor, parameters (Wrr, Wri, Wii, Br, Bi over num_features // 2 complex channels), buffers (RMr, RMi,
+    RVrr, RVri, RVii, num_batches_tracked), `reset_parameters` (Wri ~ U(-0.9, 0.9)) and forward over any [B, C, *rest]: training mode normalises with
+    the batch statistics and moves the running ones by `momentum`; eval mode uses the running statistics and leaves the buffers alone.  Differentiable
+    in the input and the parameters (ComplexBatchNorm plan, csrc/plan_layers.cpp; kernels csrc/cbn.hip).  Inside DCCRN(use_cbn=True) a holder."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, complex_axis=1):
+        super().__init__()
+        if num_features % 8:
+            raise NotImplementedError(f"sefd ComplexBatchNorm: num_features {num_features} is not a multiple of 8 (the kernels move 4 complex channels per lane)")
+        if not affine:
+            raise NotImplementedError("sefd ComplexBatchNorm: affine=False is not built")
+        if not track_running_stats:
+            raise NotImplementedError("sefd ComplexBatchNorm: track_running_stats=False is not built")
+        if momentum is None:
+            raise NotImplementedError("sefd ComplexBatchNorm: momentum=None (a cumulative average) is not built")
+        if complex_axis != 1:
+            raise NotImplementedError(f"sefd ComplexBatchNorm: complex_axis {complex_axis} is not built (the channel axis, 1, only)")
+        self.num_features, self.eps, self.momentum = num_features // 2, eps, momentum
+        self.affine, self.track_running_stats, self.complex_axis = affine, track_running_stats, complex_axis
+        h = self.num_features
+        for name in ("Wrr", "Wri", "Wii", "Br", "Bi"):
+            setattr(self, name, nn.Parameter(torch.empty(h)))
+        self.register_buffer("RMr", torch.zeros(h))
+        self.register_buffer("RMi", torch.zeros(h))
+        self.register_buffer("RVrr", torch.ones(h))
+        self.register_buffer("RVri", torch.zeros(h))
+        self.register_buffer("RVii", torch.ones(h))
+        self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+        self.reset_parameters()
+        self.act_dtype = cfg.act_dtype
+        self._init_runtime_state()
+
+    def reset_running_stats(self):
+        with torch.no_grad():
+            self.RMr.zero_()
+            self.RMi.zero_()
+            self.RVrr.fill_(1)
+            self.RVri.zero_()
+            self.RVii.fill_(1)
+            self.num_batches_tracked.zero_()
+
+    def reset_parameters(self):
+        self.reset_running_stats()
+        with torch.no_grad():
+            self.Br.zero_()
+            self.Bi.zero_()
+            self.Wrr.fill_(1)
+            self.Wri.uniform_(-.9, +.9)
+            self.Wii.fill_(1)
+
+    def extra_repr(self):
+        return (f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, affine={self.affine}, "
+                f"track_running_stats={self.track_running_stats}")
+
+    def forward(self, inputs):
+        _check_frontend_input("ComplexBatchNorm", inputs)
+        C2 = 2 * self.num_features
+        if inputs.dim() < 3 or inputs.shape[1] != C2:
+            raise ValueError(f"ComplexBatchNorm takes [B, {C2}, *rest] with at least one trailing dimension, got {tuple(inputs.shape)}")
+        B, S = inputs.shape[0], int(inputs[0, 0].numel())
+        device = inputs.device
+        if not self._flat_ok(device):
+            self._flatten(device)
+        key = ("cbn", B, S, bool(self.training), float(self.eps), float(self.momentum), self.act_dtype, str(device))
+        rt = self._runtimes.get(key)
+        if rt is None:
+            plan = Plan(B, S, act_dtype=self.act_dtype, training=bool(self.training), model="ComplexBatchNorm",
+                        cbn=dict(num_features=C2, eps=self.eps, momentum=self.momentum))
+            rt = _layer_arenas(self, plan, device)
+            self._runtimes[key] = rt
+        if self.training:
+            self._flat_nbt += 1
+        y = _LayerFunction.apply(self, rt, inputs.contiguous().view(B, C2, S), (B, C2, S), *[q for _, q in self._trainable()])
+        return y.view(inputs.shape)
+
+
+class cPReLU(nn.Module):
+    """tools_for_model.py:126-138: one PReLU for the real half of the channels and one for the imaginary half (element-wise torch)."""
+
+    def __init__(self, complex_axis=1):
+        super().__init__()
+        self.r_prelu = nn.PReLU()
+        self.i_prelu = nn.PReLU()
+        self.complex_axis = complex_axis
+
+    def forward(self, inputs):
+        real, imag = torch.chunk(inputs, 2, self.complex_axis)
+        return torch.cat([self.r_prelu(real), self.i_prelu(imag)], self.complex_axis)
+
+
+def complex_cat(inputs, axis):
+    """tools_for_model.py:184-193: concatenates the real halves, then the imaginary halves, of `inputs` along `axis`."""
+    halves = [torch.chunk(t, 2, axis) for t in inputs]
+    return torch.cat([h[0] for h in halves] + [h[1] for h in halves], axis)
+
+
 # ------------------------------------------------------------------------------------------ the models
 class DCCRN(_SefdModule):
     """Same constructor as the reference (models.py:17-28)."""
@@ -618,26 +848,6 @@ class DCCRN(_SefdModule):
         plan.io(ar, "wav", (B, L)).copy_(wav)
         plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
         return plan.io(ar, "out_real", (B, plan.NF, plan.T)).clone(), plan.io(ar, "out_imag", (B, plan.NF, plan.T)).clone()
-
-
-class RealConv2d(nn.Module):
-    """Parameter holder (tools_for_model.py:341-386)."""
-
-    def __init__(self, in_channels, out_channels, kernel_size, stride, padding):
-        super().__init__()
-        self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding=[padding[0], 0])
-        nn.init.normal_(self.conv.weight.data, std=0.05)
-        nn.init.constant_(self.conv.bias, 0.)
-
-
-class RealConvTranspose2d(nn.Module):
-    """Parameter holder (tools_for_model.py:389-425)."""
-
-    def __init__(self, in_channels, out_channels, kernel_size, stride, padding, output_padding):
-        super().__init__()
-        self.conv = nn.ConvTranspose2d(in_channels, out_channels, kernel_size, stride, padding=padding, output_padding=output_padding)
-        nn.init.normal_(self.conv.weight.data, std=0.05)
-        nn.init.constant_(self.conv.bias, 0.)
 
 
 class CRN(_SefdModule):

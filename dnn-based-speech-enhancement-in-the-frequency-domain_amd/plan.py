@@ -14,6 +14,7 @@ MASK_MODES = {"E": 0, "C": 1, "R": 2, "Direct(None make)": 4}
 DTYPES = {"fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
 
 
+CONV_KINDS = {"ComplexConv2d": 0, "ComplexConvTranspose2d": 1, "RealConv2d": 2, "RealConvTranspose2d": 3}     # csrc/plan_layers.cpp
 FSN_NORMS = {"offline_laplace_norm": 0, "cumulative_laplace_norm": 1, "offline_gaussian_norm": 2, "cumulative_layer_norm": 3}   # tools_for_model.py:1106-1118
 
 
@@ -21,13 +22,13 @@ class Plan:
     def __init__(self, B, L, kernel_num=(32, 64, 128, 256, 256, 256), rnn_layers=2, rnn_units=256, win_len=400,
                  win_inc=100, fft_len=512, masking_mode="E", lstm="complex", skip_type=True, act_dtype="fp32",
                  kernel_size=5, training=True, model="DCCRN", fsn=None, bn_world=1, grad_buckets=1, use_cbn=False, win_type="hanning",
-                 cbn_sync=False, seq=None, feature_type="complex"):
+                 cbn_sync=False, seq=None, feature_type="complex", conv=None, cbn=None):
         self.lib = _lib.lib()
         if masking_mode not in MASK_MODES:
             raise NotImplementedError(f"masking_mode {masking_mode!r} is not on the HIP path yet")
         cfg = _lib.ModelConfig()
         cfg.model = {"DCCRN": 0, "CRN": 1, "STFT": 2, "FullSubNet": 3, "TorchSTFT": 4, "TorchISTFT": 5, "SequenceModel": 6, "ConvSTFT": 7,
-                     "ConviSTFT": 8}[model]
+                     "ConviSTFT": 8, "ConvLayer": 9, "ComplexBatchNorm": 10}[model]
         cfg.B, cfg.L = int(B), int(L)
         if model == "FullSubNet":
             # L = number of STFT frames T; kernel_num carries (sb_neighbors, fb_neighbors, look_ahead, fb_hidden, sb_hidden,
@@ -53,8 +54,24 @@ class Plan:
             # the modules on their own (csrc/plan_frontend.cpp): kernel_num[0] = feature type, 0 'complex', 1 anything else (mags, phase);
             # ConviSTFT: L = frames T
             kernel_num = (0 if feature_type == "complex" else 1,)
+        if model == "ConvLayer":
+            # one conv layer of tools_for_model.py:199-425 on its own (csrc/plan_layers.cpp): B = batch, L = input frames T; kernel_num carries (kind, C_in,
+            #   C_out, KH, KW, frequency stride, padding F, padding T, causal, output padding F, input bins F)
+            v = dict(kind="ComplexConv2d", in_channels=2, out_channels=2, kernel_size=(1, 1), stride_f=1, padding=(0, 0), causal=True, output_padding_f=0, F=1)
+            v.update(conv or {})
+            kernel_num = (CONV_KINDS[v["kind"]], v["in_channels"], v["out_channels"], v["kernel_size"][0], v["kernel_size"][1], v["stride_f"],
+                          v["padding"][0], v["padding"][1], 1 if v["causal"] else 0, v["output_padding_f"], v["F"])
+            self.conv = v
+        if model == "ComplexBatchNorm":
+            # tools_for_model.py:430-607 on its own: B = batch, L = rows per batch item (the product of the trailing dimensions); kernel_num carries
+            #   (num_features, eps, momentum), the two floats as float32 bit patterns
+            v = dict(num_features=8, eps=1e-5, momentum=0.1)
+            v.update(cbn or {})
+            bits = lambda f: int(np.float32(f).view(np.int32))
+            kernel_num = (v["num_features"], bits(v["eps"]), bits(v["momentum"]))
+            self.cbn = v
         cfg.win_len, cfg.hop, cfg.fft_len = win_len, win_inc, fft_len
-        cfg.n_layers = len(kernel_num) if model not in ("FullSubNet", "SequenceModel", "ConvSTFT", "ConviSTFT") else 0
+        cfg.n_layers = len(kernel_num) if model not in ("FullSubNet", "SequenceModel", "ConvSTFT", "ConviSTFT", "ConvLayer", "ComplexBatchNorm") else 0
         for i, k in enumerate(kernel_num):
             cfg.kernel_num[i] = int(k)
         cfg.rnn_layers, cfg.rnn_units = rnn_layers, rnn_units

@@ -24,8 +24,9 @@ typedef struct sefd_plan sefd_plan;
 /* Mirror of the config.py knobs that shape DCCRN (config.py:35-68) plus batch geometry. */
 typedef struct sefd_model_config {
   int32_t model;          /* 0 DCCRN, 1 CRN, 2 ConvSTFT front end, 3 FullSubNet, 4 torch.stft front end, 5 torch.istft,
-                             6 SequenceModel on its own, 7 ConvSTFT on its own, 8 ConviSTFT on its own (see build_plan, csrc/plan.cpp) */
-  int32_t B, L;           /* batch, samples per clip (models 3, 6 and 8: L = frames T) */
+                             6 SequenceModel on its own, 7 ConvSTFT on its own, 8 ConviSTFT on its own, 9 one conv layer on its own (ConvLayer),
+                             10 ComplexBatchNorm on its own (see build_plan, csrc/plan.cpp) */
+  int32_t B, L;           /* batch, samples per clip (models 3, 6, 8 and 9: L = frames T; model 10: L = rows per batch item) */
   int32_t win_len, hop, fft_len;
   int32_t n_layers;
   int32_t kernel_num[12]; /* cfg.dccrn_kernel_num; FullSubNet (model 3): sb/fb neighbours (each 0 .. 31), look_ahead, fb/sb hidden,
@@ -39,7 +40,16 @@ typedef struct sefd_model_config {
                              (where a bin's magnitude is exactly 0 its (mags, phase) gradient is 0; the reference has NaN there).
                              Model 8, L = T, Lout = (T - 1) hop + win_len - 2 (win_len - hop): forward in | mags, phase -> wav [B][Lout] (no clamp, overlap-add / (coff + 1e-8));
                              backward grad_wav -> grad_in | grad_mags, grad_phase.  Refused, one sentence each: T < 1, Lout <= 0, win_len > fft_len, hop outside 1 .. win_len.
-                             fft_len 512 runs the FFT kernels, any other even fft_len the framing / synthesis GEMMs and their transposes */
+                             fft_len 512 runs the FFT kernels, any other even fft_len the framing / synthesis GEMMs and their transposes;
+                             ConvLayer (model 9, tools_for_model.py:199-425, csrc/plan_layers.cpp; B = batch, L = input frames T): [0] kind (0 ComplexConv2d, 1 ComplexConvTranspose2d,
+                             2 RealConv2d, 3 RealConvTranspose2d), [1] C_in, [2] C_out (complex kinds: real + imaginary, even), [3] KH (1 .. 7), [4] KW (1 .. 4), [5] frequency stride
+                             (1 .. 2; the time stride is 1), [6] padding F (< KH), [7] padding T (< KW), [8] causal (kinds 0, 2: time padding on the left only), [9] output padding F
+                             (kinds 1, 3; < stride), [10] input bins F.  I/O fp32 in the reference layout: x [B][C_in][F][T] -> y [B][C_out][Fo][To]; grad_y -> grad_x and the flat
+                             gradients (parameters real_conv / imag_conv or conv, .weight then .bias).  Storage inside the plan: act_dtype, channels padded to multiples of 8.
+                             A geometry without an output bin or frame is refused with its numbers;
+                             ComplexBatchNorm (model 10, tools_for_model.py:430-607; B = batch, L = S, the product of the trailing dimensions): [0] num_features (real + imaginary,
+                             a multiple of 8), [1] eps, [2] momentum, both as float32 bit patterns.  x [B][C][S] -> y; grad_y -> grad_x; parameters Wrr Wri Wii Br Bi, buffers
+                             RMr RMi RVrr RVri RVii.  training = 1: batch statistics, running update; 0: running statistics, buffers untouched */
   int32_t rnn_layers, rnn_units;
   int32_t mask_mode;      /* 0 'E', 1 'C', 2 'R' (cfg.masking_mode) */
   int32_t lstm_complex;   /* cfg.lstm == 'complex' */
@@ -236,6 +246,11 @@ int32_t sefd_plan_status_set(const sefd_plan* p);
  * once, the first time the table is consulted) and is changed by these calls.  value NULL unsets a knob; sefd_tuning_get returns NULL for a knob that
  * is not set (then the built-in default applies); sefd_tuning_clear returns the table to the pairs of SEFD_TUNING (empty when it is not set).  The reference has
  * no counterpart (its behaviour is fixed by config.py); nothing here changes results beyond floating-point summation order. */
+/* One launch of the layout kernel behind OP_NCHW_CL on raw device pointers (tests, tools/convlayers_bench.py): nchw fp32 [B][C][F][T], cl (dt 0 fp32, 1 bf16)
+ * [B][Tcl][F][Cpad] (Cpad a multiple of 8, >= C), nchw frame t = cl frame t + t_off (T + t_off <= Tcl); mode 0 / 2: nchw -> cl (pad channels zero), 1 / 3: cl -> nchw.
+ * Returns 0, -1 for arguments outside that domain. */
+int32_t sefd_nchw_cl(void* nchw, void* cl, int32_t B, int32_t C, int32_t Cpad, int32_t F, int32_t T, int32_t Tcl, int32_t t_off, int32_t dt, int32_t mode,
+                     void* stream);
 void sefd_tuning_set(const char* knob, const char* value);
 const char* sefd_tuning_get(const char* knob);
 void sefd_tuning_clear(void);
