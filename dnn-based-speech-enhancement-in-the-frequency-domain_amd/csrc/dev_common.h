@@ -198,6 +198,12 @@ bool launch_cgemm256(const RunGemm& d, const ArenaBases& ab, hipStream_t st);
 bool launch_enc0_fwd(const RunGemm& d, const ArenaBases& ab, hipStream_t st);        // first encoder layer on the fp32 spectrum (enc0.hip)
 bool launch_enc0_wgrad(const RunGemm& d, const ArenaBases& ab, hipStream_t st);
 bool launch_rundirect(const RunGemm& d, const ArenaBases& ab, hipStream_t st);       // thin layers, N <= 64 (thin.hip)
+bool rundirect_takes(const RunGemm& d);                                              // ... whether it takes `d`
+bool launch_rungemm_persist(const RunGemm& d, const ArenaBases& ab, hipStream_t st); // persistent form of the 128-row LDS-DMA kernel (rungemm_persist.hip)
+int rungemm_persist_grid(const RunGemm& d);                                          // ... its grid; 0: `d` stays on rungemm_kernel
+// The kernel family launch_rungemm picks for a RUNGEMM descriptor under the knobs of the moment (sefd_plan_op_info reports it)
+enum RunFamily : int { kFamNone = 0, kFamEnc0 = 1, kFamCgemm256 = 2, kFamDirect = 3, kFamTiled = 4, kFamPersist = 5 };
+int rungemm_family(const RunGemm& d);
 void launch_misc(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st);
 void launch_istft_fft(const IstftFft& d, const ArenaBases& ab, hipStream_t st);

@@ -1241,6 +1241,9 @@ static bool launch_wgrad_rank(const RunGemm& d, const ArenaBases& ab, hipStream_
 // 256 x 128 tile (4 or 8 waves, 2- or 3-stage ring), as a 3/4-stage 128 x 128 ring (one workgroup per CU) and with the
 // fragment reads / next-stage DMAs interleaved between the MFMA groups; none of them beat two co-resident 128 x 128
 // workgroups with a 2-stage ring, so that is the only configuration launched (and the only one built).
+// Those variants all held ONE lock-step workgroup per CU.  The same tile as a persistent kernel that keeps the co-residency (two workgroups of
+// 66 KB per CU at BN = 128, three at BN = 64 / 32), starts the next tile's first ring stage before the epilogue and keeps the epilogue in
+// registers is rungemm_persist.hip; launch_rungemm_t hands it the launches it takes (knob RG_PERSIST; profiles/rungemm_persist_notes.md).
 template <typename TA, int BN>
 static void launch_rungemm_dma(const RunGemm& d, const ArenaBases& ab, hipStream_t st, int grid) {
   if (d.flags & kRunBnBwd) { hipLaunchKernelGGL((rungemm_kernel<TA, BN, true, 2, kBM, 4, false, true>), dim3(grid), dim3(256), 0, st, d, ab); return; }
@@ -1252,6 +1255,9 @@ static void launch_rungemm_t(const RunGemm& d, const ArenaBases& ab, hipStream_t
   const int bn = bn_of(d.N);
   const int nm = (d.M + kBM - 1) / kBM;
   const int grid = nm * (d.Npad / bn);
+  if constexpr (sizeof(TA) == 2) {
+    if (launch_rungemm_persist(d, ab, st)) return;         // bf16, aligned in and out, plain epilogue, enough tiles (rungemm_persist.hip)
+  }
   if (d.flags & kRunAligned) {
     if (bn == 128) launch_rungemm_dma<TA, 128>(d, ab, st, grid);
     else if (bn == 64) launch_rungemm_dma<TA, 64>(d, ab, st, grid);
@@ -1285,6 +1291,16 @@ void launch_rungemm(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
   if (launch_rundirect(d, ab, st)) return;                 // direct-operand kernel for the thin bf16 layers (thin.hip)
   if (d.xdt == DT_BF16) launch_rungemm_t<bf16_t>(d, ab, st);
   else launch_rungemm_t<float>(d, ab, st);
+}
+
+// The same decisions as launch_rungemm, without a launch (sefd_plan_op_info; the per-launch knobs are read as a launch would read them now)
+int rungemm_family(const RunGemm& d) {
+  if ((d.flags & kRunEnc0) && enc0_accepts(d, false)) return kFamEnc0;
+  if (d.flags & (kRunEnc0 | kRunDyFromBn)) return kFamNone;
+  if (d.flags & kRunWTile32) return kFamCgemm256;
+  if (rundirect_takes(d)) return kFamDirect;
+  if (d.xdt == DT_BF16 && rungemm_persist_grid(d) > 0) return kFamPersist;
+  return kFamTiled;
 }
 
 // 256 x 256 tile, 8 waves, dual form of the 4-stage ring of 32 KB = 128 KB: one workgroup per CU (wgrad_tn == 256)

@@ -241,8 +241,8 @@ __global__ __launch_bounds__(kThinWaves * 64) void rundirect_kernel(const RunGem
 }  // namespace
 
 // Chosen by shape: bf16 in / out, LDS-DMA-able (aligned) runs, no accumulate / ReLU, N <= 64 and the packed weights fit LDS next to the
-// staging pieces.
-bool launch_rundirect(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
+// staging pieces.  *wpitch_out / *lds_out: the weight row pitch and the LDS bytes of the launch.
+static bool rundirect_form(const RunGemm& d, int* wpitch_out, size_t* lds_out) {
   // measured (profiles/r03_tuning_notes.md): fragment-shaped loads run at the line rate of the vector memory pipe (32 rows x 32 B per
   // instruction: ~6 TB/s of operand bytes), so the kernel wins only where K is tiny (enc0, the mask layer's input gradient: ldw = 128,
   // 92 -> 64-72 us) and loses from K = 320 on (dec4: 139 -> 255 us); larger K stays on the tiled LDS-DMA kernel
@@ -254,6 +254,15 @@ bool launch_rundirect(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
   const int wpitch = d.ldw * 2 + 16;
   const size_t lds = (size_t)d.Npad * wpitch + kThinWaves * 2048;
   if (lds > 100 * 1024) return false;
+  *wpitch_out = wpitch; *lds_out = lds;
+  return true;
+}
+bool rundirect_takes(const RunGemm& d) { int wp; size_t lds; return rundirect_form(d, &wp, &lds); }   // (rungemm_family, rungemm.hip)
+
+bool launch_rundirect(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
+  int wpitch = 0;
+  size_t lds = 0;
+  if (!rundirect_form(d, &wpitch, &lds)) return false;
   const int blocks = (d.M + kThinRows - 1) / kThinRows;
   const dim3 grid((blocks + kThinWaves - 1) / kThinWaves);
   auto go = [&](auto kern) {

@@ -9,6 +9,8 @@ from . import _lib
 
 ARENA_WS, ARENA_PARAM, ARENA_GRAD, ARENA_STATE, ARENA_CONST, ARENA_IO, ARENA_COUNT = 0, 1, 2, 3, 4, 5, 6
 PHASE_FWD, PHASE_BWD = 0, 1
+# op_info()["family"] of a RUNGEMM op (csrc/dev_common.h RunFamily)
+RUN_FAMILY_NONE, RUN_FAMILY_ENC0, RUN_FAMILY_CGEMM256, RUN_FAMILY_DIRECT, RUN_FAMILY_TILED, RUN_FAMILY_PERSIST = range(6)
 RUN_WAVE_ONLY = 1
 MASK_MODES = {"E": 0, "C": 1, "R": 2, "Direct(None make)": 4}
 DTYPES = {"fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -162,12 +164,13 @@ class Plan:
         return raw[:, 0].copy(), raw[:, 1].copy()
 
     def op_info(self, phase, i):
-        """dict(kind, tag, M, N, K, dtype, flops, bytes) of op i (RUNGEMM / WGRAD carry the GEMM geometry)."""
+        """dict(kind, tag, M, N, K, dtype, flags, family, flops, bytes) of op i (RUNGEMM / WGRAD carry the GEMM geometry).  family (RUNGEMM): the
+        kernel a launch would pick under the tuning table of the moment - one of the RUN_FAMILY_* values below."""
         o = (C.c_int64 * 8)()
         if self.lib.sefd_plan_op_info(self.h, phase, i, o) != 0:
             raise IndexError(i)
-        return dict(kind=int(o[0]), tag=int(o[1]), M=int(o[2]), N=int(o[3]), K=int(o[4]), dtype=int(o[5]) & 0xff, flags=int(o[5]) >> 8,
-                    flops=int(o[6]), bytes=int(o[7]))
+        return dict(kind=int(o[0]), tag=int(o[1]), M=int(o[2]), N=int(o[3]), K=int(o[4]), dtype=int(o[5]) & 0xff, flags=(int(o[5]) >> 8) & 0xffffffff,
+                    family=(int(o[5]) >> 48) & 0xff, flops=int(o[6]), bytes=int(o[7]))
 
     def buffer(self, name):
         a, off, nb, dt = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32()

@@ -103,7 +103,9 @@ const void* sefd_plan_const_data(const sefd_plan* p);
 int32_t sefd_plan_num_ops(const sefd_plan* p, int phase);
 const void* sefd_plan_ops(const sefd_plan* p, int phase);
 int32_t sefd_op_size(void);
-/* per-op summary for measurement: out = {kind, tag, M, N, K (true run length), operand dtype, algorithmic flops, algorithmic bytes} */
+/* per-op summary for measurement: out = {kind, tag, M, N, K (true run length), operand dtype, algorithmic flops, algorithmic bytes};
+   out[5] of a GEMM op: bits 0-7 operand dtype, bits 8-39 descriptor flags, bits 48-55 (RUNGEMM) the kernel family a launch would pick under the
+   tuning table of the moment: 1 first-layer, 2 wide-tile, 3 direct-operand, 4 tiled (one tile per workgroup), 5 persistent tiled, 0 none */
 int32_t sefd_plan_op_info(const sefd_plan* p, int phase, int i, int64_t* out8);
 
 /* ---- execution (device) --------------------------------------------------------------------------
