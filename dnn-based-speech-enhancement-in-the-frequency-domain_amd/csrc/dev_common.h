@@ -214,6 +214,8 @@ void launch_fsn(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_bn(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_cbn(const Op& op, const ArenaBases& ab, hipStream_t st);       // ComplexBatchNorm (cbn.hip)
 void launch_lstm_bf16(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd);
+// the reversed groups of a persistent launch (LstmRec::rev_mask over its at most 4 groups): != 0 selects the direction-aware instantiations
+inline int lstm_rev_groups(const LstmRec& d) { return d.rev_mask & ((1 << (d.G < 4 ? d.G : 4)) - 1); }
 void launch_lstm_cluster(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd);   // H > 128 (lstm_cluster.hip)
 void launch_lstm_rows(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd);      // impl == 1 (lstm_rows.hip)
 bool launch_lstm_rows_pair(const LstmRec& d0, const LstmRec& d1, const ArenaBases& ab, hipStream_t st);   // two stacked forward layers, one launch

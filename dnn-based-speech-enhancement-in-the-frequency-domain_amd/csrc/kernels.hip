@@ -345,12 +345,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdApply d, c
 // lane-local.  W_hh stays in VGPRs for the whole sequence as fp32 MFMA B-fragments (4 gates x H/4 k-steps = H registers);
 // only h_t crosses waves, through a double-buffered LDS tile.  v_mfma_f32_16x16x4_f32: A[i=l&15][k=l>>4], B[k=l>>4][j=l&15],
 // D[row=4*(l>>4)+r][col=l&15].
-template <int HMAX>
+// DIR: some group of the launch walks the frames backwards (LstmRec::rev_mask): logical step t of a reversed group is physical frame T - 1 - t, its
+// predecessor the frame after it.  The loop, the LDS double buffer and the prefetch count logical steps; fr(t) is the frame a step reads and writes.
+template <int HMAX, bool DIR>
 __global__ __launch_bounds__(HMAX * 4) void lstm_fwd_kernel(const LstmRec d, const ArenaBases ab) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int H = d.H, T = d.T;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int g = blockIdx.y, b0 = blockIdx.x * 16;
+  const bool rev = DIR && ((d.rev_mask >> g) & 1);
+  auto fr = [&](int t) { return rev ? T - 1 - t : t; };
   const int set = g % d.nset;
   const float* whh = reinterpret_cast<const float*>(rp(ab, d.whh[set]));
   const float* gx = reinterpret_cast<const float*>(rp(ab, d.gx)) + d.gx_goff[g];
@@ -387,7 +391,7 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_fwd_kernel(const LstmRec d, con
     for (int q = 0; q < 4; ++q)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        gxv[q][r] = gx[(rowbt[r] + t) * d.gx_ld + gate_col(q, unit)];     // rows >= B alias row 0, never stored
+        gxv[q][r] = gx[(rowbt[r] + fr(t)) * d.gx_ld + gate_col(q, unit)];     // rows >= B alias row 0, never stored
   };
   load_gx(0);
   const int64_t GBT = (int64_t)d.B * T;
@@ -417,7 +421,7 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_fwd_kernel(const LstmRec d, con
       const float h = og * tanhf_(c[r]);
       lds[hn + (4 * kq + r) * hs + unit] = h;
       if (rvalid[r]) {
-        const int64_t row = (int64_t)g * GBT + rowbt[r] + t;
+        const int64_t row = (int64_t)g * GBT + rowbt[r] + fr(t);
         st_elem(hout, d.hdt, row * H + unit, h);
         *reinterpret_cast<float4*>(gates + (row * H + unit) * 4) = make_float4(ig, fg, gg, og);
         cs[row * H + unit] = c[r];
@@ -429,12 +433,16 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_fwd_kernel(const LstmRec d, con
 
 // Backward through time.  Per step: lane-local gate gradients -> LDS [16][4H] -> dh_{t-1} = dgates_t . W_hh on the MFMA
 // (contraction over all 4H gate columns, W_hh^T slice of this wave's 16 units resident in H VGPRs).
-template <int HMAX>
+// DIR as in the forward kernel: the backward of a reversed group visits the physical frames 0 -> T - 1 (t stays the logical step) and hands dh to frame t + 1.
+template <int HMAX, bool DIR>
 __global__ __launch_bounds__(HMAX * 4) void lstm_bwd_kernel(const LstmRec d, const ArenaBases ab) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int H = d.H, T = d.T;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int g = blockIdx.y, b0 = blockIdx.x * 16;
+  const bool rev = DIR && ((d.rev_mask >> g) & 1);
+  auto fr = [&](int t) { return rev ? T - 1 - t : t; };
+  const int prev = rev ? -1 : 1;                // rows back to the frame of the previous logical step
   const int set = g % d.nset;
   const float* whh = reinterpret_cast<const float*>(rp(ab, d.whh[set]));
   const float* gates = reinterpret_cast<const float*>(rp(ab, d.gates));
@@ -466,16 +474,16 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_bwd_kernel(const LstmRec d, con
   auto fetch = [&](int t, float (&g4)[4][4], float (&cp)[4], float (&dhv)[4]) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int64_t row = (int64_t)g * GBT + rowbt[r] + t;
+      const int64_t row = (int64_t)g * GBT + rowbt[r] + fr(t);
 #pragma unroll
       for (int q = 0; q < 4; ++q) g4[r][q] = gates[(row * H + unit) * 4 + q];      // rows >= B alias row 0, results unused
-      cp[r] = cs[(row - (t > 0 ? 1 : 0)) * H + unit];
+      cp[r] = cs[(row - (t > 0 ? prev : 0)) * H + unit];
       dhv[r] = dh[row * H + unit];
     }
   };
   fetch(T - 1, pg, pcp, pdh);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) pct[r] = cs[((int64_t)g * GBT + rowbt[r] + T - 1) * H + unit];
+  for (int r = 0; r < 4; ++r) pct[r] = cs[(rev ? (int64_t)g * GBT + rowbt[r] : (int64_t)g * GBT + rowbt[r] + T - 1) * H + unit];
   for (int t = T - 1; t >= 0; --t) {
     if (t > 0) fetch(t - 1, ng, ncp, ndh);
 #pragma unroll
@@ -493,7 +501,7 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_bwd_kernel(const LstmRec d, con
         df = dc * cp * fg * (1.f - fg);
         dg = dc * ig * (1.f - gg * gg);
         dcarry[r] = dc * fg;
-        const int64_t o = d.gx_goff[g] + (rowbt[r] + t) * d.gx_ld;
+        const int64_t o = d.gx_goff[g] + (rowbt[r] + fr(t)) * d.gx_ld;
         st_elem(dgo, d.gdt, o + gate_col(0, unit), di);
         st_elem(dgo, d.gdt, o + gate_col(1, unit), df);
         st_elem(dgo, d.gdt, o + gate_col(2, unit), dg);
@@ -831,18 +839,33 @@ __global__ __launch_bounds__(256) void specout_bwd_kernel(const SpecOut d, const
 }
 
 // ------------------------------------------------------------------------------------------------ dispatch
-template <int HMAX>
-static void launch_lstm(const Op& op, const ArenaBases& ab, hipStream_t st, bool fwd) {
-  const LstmRec& d = op.lstm;
+__global__ void lstm_refuse_kernel(int* host_word, int* dev_word) { set_status(host_word, dev_word); }
+
+template <int HMAX, bool DIR>
+static void launch_lstm_dir(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd) {
   dim3 grid((d.B + 15) / 16, d.G);
   dim3 block(64 * (d.H / 16));
   if (fwd) {
     const size_t sh = 2 * 16 * (d.H + 2) * sizeof(float);
-    hipLaunchKernelGGL((lstm_fwd_kernel<HMAX>), grid, block, sh, st, d, ab);
+    hipLaunchKernelGGL((lstm_fwd_kernel<HMAX, DIR>), grid, block, sh, st, d, ab);
   } else {
     const size_t sh = 16 * (4 * d.H + 2) * sizeof(float);
-    hipLaunchKernelGGL((lstm_bwd_kernel<HMAX>), grid, block, sh, st, d, ab);
+    hipLaunchKernelGGL((lstm_bwd_kernel<HMAX, DIR>), grid, block, sh, st, d, ab);
   }
+}
+
+template <int HMAX>
+static void launch_lstm(const Op& op, const ArenaBases& ab, hipStream_t st, bool fwd) {
+  const LstmRec& d = op.lstm;
+  // reversed groups (LstmRec::rev_mask): the direction-aware instantiations, for whole-sequence launches of at most 4 groups only - anything else is
+  // not launched and the plan's status word says so (as launch_lstm_bf16 / launch_lstm_cluster do).  These kernels never resume (t0 / t1 are not read)
+  const int mask = lstm_rev_groups(d);
+  if (mask != 0 && (d.t0 != 0 || d.t1 != 0 || d.G > 4)) {
+    hipLaunchKernelGGL(lstm_refuse_kernel, dim3(1), dim3(1), 0, st, ab.status, ab.dstatus);
+    return;
+  }
+  if (mask != 0) launch_lstm_dir<HMAX, true>(d, ab, st, fwd);
+  else launch_lstm_dir<HMAX, false>(d, ab, st, fwd);
 }
 
 // ---- two-level BatchNorm finalize (training, per-rank statistics; forward and backward) ------------------------------------------------

@@ -34,13 +34,18 @@ __device__ __forceinline__ f32x2 tanh2(f32x2 x) { return fma2(rcp_2(exp2_2(x * 2
 // issues (5 exp + 5 rcp per cell at quarter rate), not by the MFMAs, and the recurrence of a DCCRN step (B = 32, 4 groups) fills 8 of
 // 256 CUs - four times the workgroups, a quarter of the per-step issue (forward LSTM of the default step: 1.03 -> ~0.4 ms exposed).
 // The per-element arithmetic is the same in both variants (same operations in the same order), only the packing differs.
-template <int HMAX, int RPW>
+// DIR: some group of the launch walks the frames backwards (LstmRec::rev_mask, the reverse direction of a bidirectional layer): logical step s of a
+// reversed group is physical frame T - 1 - s and its predecessor the frame after it.  Steps, the LDS double buffer and the prefetch ring are counted in
+// logical steps; only the addresses of gx, h, c and the saved gates run the other way (the prefetch clamp of the last logical step is then frame 0).
+// Such a launch covers the whole sequence (the launcher refuses t0 / t1).  With DIR = false the strides below are the compile-time constants they were.
+template <int HMAX, int RPW, bool DIR>
 __global__ __launch_bounds__(HMAX * 4) void lstm_fwd_bf16_kernel(const LstmRec d, const ArenaBases ab) {
   extern __shared__ __attribute__((aligned(16))) uint16_t ldsh[];
   constexpr int H = HMAX;
   const int T = d.T;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int g = blockIdx.y, b0 = blockIdx.x * RPW;
+  const bool rev = DIR && ((d.rev_mask >> g) & 1);
   constexpr int NR = RPW == 16 ? 4 : 1;            // cells per lane
   const float* whh = reinterpret_cast<const float*>(rp(ab, d.whh[g % d.nset]));
   const float* gx = reinterpret_cast<const float*>(rp(ab, d.gx)) + d.gx_goff[g];
@@ -84,17 +89,19 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_fwd_bf16_kernel(const LstmRec d
   const int64_t GBT = (int64_t)d.B * T;
   const float* gxp[NR];                          // gx of (row r, this unit), current prefetch position
   int64_t so[NR];                               // (g*GBT + row*T + t) * H + unit : element offset of the cell in h / c, x4 in gates
+  const int f0 = rev ? T - 1 : tb;              // physical frame of the first step
+  const int64_t hstep = rev ? -H : H;           // one logical step in h / c
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
-    gxp[r] = gx + (rowbt[r] + tb) * d.gx_ld + gate_col(0, unit);     // rows >= B alias row 0, never stored
-    so[r] = ((int64_t)g * GBT + rowbt[r] + tb) * H + unit;
+    gxp[r] = gx + (rowbt[r] + f0) * d.gx_ld + gate_col(0, unit);     // rows >= B alias row 0 (in either direction), never stored
+    so[r] = ((int64_t)g * GBT + rowbt[r] + f0) * H + unit;
     if (tb > 0) {                                                    // h[tb-1] into the LDS buffer step tb reads, c[tb-1] into registers
       c[r] = cs[so[r] - H];
       ldsh[(tb & 1) * 16 * hs + (4 * kq + r) * hs + unit] = hout[so[r] - H];
     }
   }
   if (tb > 0) __syncthreads();
-  const int64_t gx_ld = d.gx_ld;
+  const int64_t gx_ld = rev ? -(int64_t)d.gx_ld : (int64_t)d.gx_ld;    // one logical step in gx
   auto load_gx = [&](int t, float4 (&dst)[NR]) {                        // t is clamped: the last two prefetches re-read step T-1
     const int64_t inc = t < T - 1 ? gx_ld : 0;
 #pragma unroll
@@ -138,7 +145,7 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_fwd_bf16_kernel(const LstmRec d
           *reinterpret_cast<float4*>(gates + so[r] * 4) = make_float4(ig[k], fg[k], gg[k], og[k]);
           cs[so[r]] = cn[k];
         }
-        so[r] += H;
+        so[r] += hstep;
       }
     }
     } else {
@@ -155,7 +162,7 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_fwd_bf16_kernel(const LstmRec d
         *reinterpret_cast<float4*>(gates + so[0] * 4) = make_float4(s.x, s.y, gg, og);
         cs[so[0]] = cn;
       }
-      so[0] += H;
+      so[0] += hstep;
     }
     lds_barrier();
   };
@@ -175,13 +182,16 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_fwd_bf16_kernel(const LstmRec d
 // RPW as in the forward kernel.  4: the sequences sit in rows 0, 4, 8, 12 of the dgates tile (A operand), so the accumulator row a lane
 // reads back (row 4*kq of dh_{t-1} = dgates_t . W_hh) is the ONE cell whose gate gradients it forms: a quarter of the loads and of the
 // gate math per lane and four times the workgroups (DCCRN step: 8 -> 32 of 256 CUs).  Same operations in the same order per element.
-template <int HMAX, int RPW>
+// DIR as in the forward kernel: the backward of a reversed group walks the physical frames 0 -> T - 1 and hands dh to frame t + 1.  `t` below stays the
+// logical step (T - 1 down to 0, so the three-frame rotation and its tails are the same); the fetch and store positions move the other way.
+template <int HMAX, int RPW, bool DIR>
 __global__ __launch_bounds__(HMAX * 4) void lstm_bwd_bf16_kernel(const LstmRec d, const ArenaBases ab) {
   extern __shared__ __attribute__((aligned(16))) uint16_t ldsh[];
   constexpr int H = HMAX;
   const int T = d.T;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int g = blockIdx.y, b0 = blockIdx.x * RPW;
+  const bool rev = DIR && ((d.rev_mask >> g) & 1);
   constexpr int NR = RPW == 16 ? 4 : 1;            // cells per lane
   const float* whh = reinterpret_cast<const float*>(rp(ab, d.whh[g % d.nset]));
   const float* gates = reinterpret_cast<const float*>(rp(ab, d.gates));
@@ -214,11 +224,13 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_bwd_bf16_kernel(const LstmRec d
   bool rvalid[NR];
   int64_t fo[NR];                               // fetch position: (g*GBT + row*T + t) * H + unit
   const int64_t GBT = (int64_t)d.B * T;
+  const int fl = rev ? 0 : T - 1;               // physical frame of the last logical step, where the walk starts
+  const int64_t hback = rev ? -H : H;           // one logical step back in h / c / dh
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
     const int b = RPW == 16 ? b0 + 4 * kq + r : b0 + kq;
     rvalid[r] = b < d.B;
-    fo[r] = ((int64_t)g * GBT + (int64_t)(rvalid[r] ? b : 0) * T + (T - 1)) * H + unit;   // rows >= B alias row 0, results unused
+    fo[r] = ((int64_t)g * GBT + (int64_t)(rvalid[r] ? b : 0) * T + fl) * H + unit;   // rows >= B alias row 0 (in either direction), results unused
   }
   // dgates_t leave through the LDS tile with 16-byte stores: H/2 chunks per sequence; RPW 16: 2 chunks per thread (tile rows w', w'+8),
   // RPW 4: threads 0 .. 2H-1 move one chunk each (tile rows 0, 4, 8, 12)
@@ -233,16 +245,16 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_bwd_bf16_kernel(const LstmRec d
     const int b = RPW == 16 ? b0 + crow + 8 * i : b0 + crow;
     drow[i] = RPW == 16 ? crow + 8 * i : 4 * (crow & 3);
     dvalid[i] = b < d.B && (RPW == 16 || crow < 4);
-    dptr[i] = dgo + d.gx_goff[g] + ((int64_t)(dvalid[i] ? b : 0) * T + (T - 1)) * d.gx_ld + cc8 * 8;
+    dptr[i] = dgo + d.gx_goff[g] + ((int64_t)(dvalid[i] ? b : 0) * T + fl) * d.gx_ld + cc8 * 8;
   }
-  const int64_t gx_ld = d.gx_ld;
+  const int64_t gx_ld = rev ? -(int64_t)d.gx_ld : (int64_t)d.gx_ld;    // one logical step back in dgates
 
   float dcarry[NR] = {};
   f32x4 dhrec = {0.f, 0.f, 0.f, 0.f};
   // software prefetch ring, two steps of look-ahead (one step does not cover an HBM round trip); unrolled, no copies
   struct Sav { float4 g[NR]; float cp[NR], dh[NR]; };
-  auto fetch = [&](int t_, Sav& s) {            // reads the current position, then steps back one frame (stays at frame 0)
-    const int64_t back = t_ > 0 ? H : 0;
+  auto fetch = [&](int t_, Sav& s) {            // reads the current position, then steps back one logical step (stays at step 0)
+    const int64_t back = t_ > 0 ? hback : 0;
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
       s.g[r] = *reinterpret_cast<const float4*>(gates + fo[r] * 4);
@@ -330,7 +342,7 @@ __global__ __launch_bounds__(HMAX * 4) void lstm_bwd_bf16_kernel(const LstmRec d
   if (t >= 0) { step(t, s1, s0); --t; }
 }
 
-template <int HMAX>
+template <int HMAX, bool DIR>
 static void launch_t(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd) {
   dim3 grid((d.B + 15) / 16, d.G);
   dim3 block(64 * (d.H / 16));
@@ -339,19 +351,34 @@ static void launch_t(const LstmRec& d, const ArenaBases& ab, hipStream_t st, boo
   const int rpw_both = (int)tune_int("LSTM_RPW", 0);
   const int rpw_env = fwd ? rpw_both : (int)tune_int("LSTM_RPW_BWD", rpw_both);
   const bool spread = rpw_env ? rpw_env == 4 : (int64_t)((d.B + 3) / 4) * d.G <= 1024;      // one cell per lane while the chip has CUs to spare
-  if (fwd && spread) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<HMAX, 4>), dim3((d.B + 3) / 4, d.G), block, 2 * 16 * (d.H + 8) * sizeof(uint16_t), st, d, ab);
-  else if (fwd) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<HMAX, 16>), grid, block, 2 * 16 * (d.H + 8) * sizeof(uint16_t), st, d, ab);
-  else if (spread) hipLaunchKernelGGL((lstm_bwd_bf16_kernel<HMAX, 4>), dim3((d.B + 3) / 4, d.G), block, 16 * (4 * d.H + 8) * sizeof(uint16_t), st, d, ab);
-  else hipLaunchKernelGGL((lstm_bwd_bf16_kernel<HMAX, 16>), grid, block, 16 * (4 * d.H + 8) * sizeof(uint16_t), st, d, ab);
+  if (fwd && spread) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<HMAX, 4, DIR>), dim3((d.B + 3) / 4, d.G), block, 2 * 16 * (d.H + 8) * sizeof(uint16_t), st, d, ab);
+  else if (fwd) hipLaunchKernelGGL((lstm_fwd_bf16_kernel<HMAX, 16, DIR>), grid, block, 2 * 16 * (d.H + 8) * sizeof(uint16_t), st, d, ab);
+  else if (spread) hipLaunchKernelGGL((lstm_bwd_bf16_kernel<HMAX, 4, DIR>), dim3((d.B + 3) / 4, d.G), block, 16 * (4 * d.H + 8) * sizeof(uint16_t), st, d, ab);
+  else hipLaunchKernelGGL((lstm_bwd_bf16_kernel<HMAX, 16, DIR>), grid, block, 16 * (4 * d.H + 8) * sizeof(uint16_t), st, d, ab);
 }
 
-void launch_lstm_bf16(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd) {
+template <bool DIR>
+static void launch_h(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd) {
   switch (d.H) {          // planner guarantees H % 32 == 0, H <= 128 and gdt == bf16 in bf16 mode
-    case 32: launch_t<32>(d, ab, st, fwd); break;
-    case 64: launch_t<64>(d, ab, st, fwd); break;
-    case 96: launch_t<96>(d, ab, st, fwd); break;
-    default: launch_t<128>(d, ab, st, fwd); break;
+    case 32: launch_t<32, DIR>(d, ab, st, fwd); break;
+    case 64: launch_t<64, DIR>(d, ab, st, fwd); break;
+    case 96: launch_t<96, DIR>(d, ab, st, fwd); break;
+    default: launch_t<128, DIR>(d, ab, st, fwd); break;
   }
+}
+
+__global__ void lstm_bf16_refuse_kernel(int* host_word, int* dev_word) { set_status(host_word, dev_word); }
+
+void launch_lstm_bf16(const LstmRec& d, const ArenaBases& ab, hipStream_t st, bool fwd) {
+  // a reversed group resumes from no saved state: its launch covers the whole sequence (t0 = t1 = 0), of at most 4 groups (gx_goff).  Anything else is
+  // not launched; the plan's status word says so, as the cluster launcher does (lstm_cluster.hip).  The DIR instantiations run only when a group is reversed
+  const int mask = lstm_rev_groups(d);
+  if (mask != 0 && (d.t0 != 0 || d.t1 != 0 || d.G > 4)) {
+    hipLaunchKernelGGL(lstm_bf16_refuse_kernel, dim3(1), dim3(1), 0, st, ab.status, ab.dstatus);
+    return;
+  }
+  if (mask != 0) launch_h<true>(d, ab, st, fwd);
+  else launch_h<false>(d, ab, st, fwd);
 }
 
 }  // namespace sefd

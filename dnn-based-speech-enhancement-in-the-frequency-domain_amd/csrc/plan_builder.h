@@ -11,7 +11,7 @@
 //
 // This header: what every planner shares - the front-end geometry (Stft) and the Builder (arenas, parameter tables, op list, GEMM
 // descriptors, the conv stack, the recurrent block, weight gradients and their UNPACK).  The planners: plan_dccrn.cpp, plan_crn.cpp,
-// plan_fsn.cpp, plan_seq.cpp, plan_frontend.cpp; the post-pass over a finished plan and build_plan(): plan.cpp.
+// plan_fsn.cpp, plan_seq.cpp, plan_clstm.cpp, plan_frontend.cpp; the post-pass over a finished plan and build_plan(): plan.cpp.
 #pragma once
 #include "plan.h"
 #include "tuning.h"
@@ -941,5 +941,6 @@ Plan* build_convstft_plan(const ModelConfig& cfg);
 Plan* build_convistft_plan(const ModelConfig& cfg);
 Plan* build_convlayer_plan(const ModelConfig& cfg);
 Plan* build_cbn_plan(const ModelConfig& cfg);
+Plan* build_clstm_plan(const ModelConfig& cfg);
 
 }  // namespace sefd

@@ -243,9 +243,12 @@ struct LstmRec {
   // wpk_f with ONE k-step: rows_wf_index(32, c, k)) + h_{t-1} . W_hh^T; `gx` is not read (no 8 GB pre-activation slab to write and re-read)
   Ptr xin, wpk_x, bias;
   int32_t xfeat;
-  int32_t rev_mask;            // cluster kernels (lstm_cluster.hip) only, formerly a pad word: bit g set = group g walks the frames backwards, logical step s =
-                               // physical frame T - 1 - s (the reverse direction of a bidirectional layer beside the forward one: G = 2, mask 0b10).  Such a
-                               // launch covers the whole sequence (t0 = t1 = 0); 0 in every plan that has no direction
+  int32_t rev_mask;            // formerly a pad word: bit g set = group g (of at most 4) walks the frames backwards, logical step s = physical frame T - 1 - s, its
+                               // predecessor the frame after it (the reverse direction of a bidirectional layer).  Read by the cluster kernels (lstm_cluster.hip:
+                               // SequenceModel, G = 2, mask 0b10 beside the forward group) and by the persistent H <= 128 kernels (kernels.hip, lstm_bf16.hip: the
+                               // ComplexLSTM plan, a launch of its own with G = 4, mask 0b1111), in their DIR instantiations; not by the row-block kernels (impl 1).
+                               // Such a launch covers the whole sequence (t0 = t1 = 0; the launchers refuse anything else through the plan's status word);
+                               // 0 in every plan that has no direction
   // impl 1, forward, hd != A_NONE: the inverted dropout that follows the layer (struct Dropout: seed, keep, layer) is applied while h_t is
   // stored - hd [T][rows][H] (dtype hdt) = h * scale, no separate pass over the 2 GB h array
   // backward, seed != A_NONE: `dh` is the gradient w.r.t. the DROPPED h: it is multiplied by the same mask as it is loaded

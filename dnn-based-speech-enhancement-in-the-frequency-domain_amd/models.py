@@ -142,23 +142,7 @@ class ConviSTFT(nn.Module):
         return wav.unsqueeze(1)
 
 
-# (ComplexConv2d, ComplexConvTranspose2d, ComplexBatchNorm: below, on _SefdModule)
-
-
-class NavieComplexLSTM(nn.Module):
-    """Parameter holder (tools_for_model.py:141-160)."""
-
-    def __init__(self, input_size, hidden_size, projection_dim=None, bidirectional=False, batch_first=False):
-        super().__init__()
-        self.input_dim, self.rnn_units = input_size // 2, hidden_size // 2
-        self.real_lstm = nn.LSTM(self.input_dim, self.rnn_units, num_layers=1, bidirectional=False, batch_first=False)
-        self.imag_lstm = nn.LSTM(self.input_dim, self.rnn_units, num_layers=1, bidirectional=False, batch_first=False)
-        if projection_dim is not None:
-            self.projection_dim = projection_dim // 2
-            self.r_trans = nn.Linear(self.rnn_units, self.projection_dim)
-            self.i_trans = nn.Linear(self.rnn_units, self.projection_dim)
-        else:
-            self.projection_dim = None
+# (ComplexConv2d, ComplexConvTranspose2d, ComplexBatchNorm, NavieComplexLSTM: below, on _SefdModule)
 
 
 # ------------------------------------------------------------------------------------------ device runtime
@@ -721,6 +705,104 @@ class ComplexBatchNorm(_SefdModule):
             self._flat_nbt += 1
         y = _LayerFunction.apply(self, rt, inputs.contiguous().view(B, C2, S), (B, C2, S), *[q for _, q in self._trainable()])
         return y.view(inputs.shape)
+
+
+class _CLSTMFunction(torch.autograd.Function):
+    """One ComplexLSTM plan (csrc/plan_clstm.cpp) at its batch-major boundary: x [B, T, 2 IP] (real | imaginary) -> y [B, T, 2 P], or without a
+    projection the directions' combined outputs [D, B, T, 2 H].  The saved activations live in the runtime's workspace (stamp, as _LayerFunction)."""
+
+    @staticmethod
+    def forward(ctx, owner, rt, x, *params):
+        plan, ar = rt
+        plan.io(ar, "x", tuple(x.shape)).copy_(x)
+        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
+        plan.stamp = getattr(plan, "stamp", 0) + 1
+        B, T = x.shape[0], x.shape[1]
+        D, H, P = (2 if owner.bidirectional else 1), owner.rnn_units, owner.projection_dim
+        ctx.owner, ctx.rt, ctx.in_shape, ctx.stamp = owner, rt, tuple(x.shape), plan.stamp
+        ctx.out_shape = (B, T, 2 * P) if P is not None else (D, B, T, 2 * H)
+        if P is not None:
+            return plan.io(ar, "y", ctx.out_shape).clone()
+        return plan.view(ar, "hc").view(ctx.out_shape).to(torch.float32, copy=True)      # activation dtype -> fp32 at the boundary
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        plan, ar = ctx.rt
+        if ctx.stamp != plan.stamp:
+            raise RuntimeError("sefd: a later forward of the same shape overwrote the activations this backward needs")
+        plan.io(ar, "grad_y", ctx.out_shape).copy_(g)
+        plan.run(PHASE_BWD, ar, torch.cuda.current_stream().cuda_stream)
+        flat = ctx.owner._flat_grad.clone()
+        return (None, None, plan.io(ar, "grad_x", ctx.in_shape).clone()) + tuple(
+            flat[off:off + n].view(shape) for (off, n, shape) in ctx.owner._param_slices)
+
+
+class NavieComplexLSTM(_SefdModule):
+    """tools_for_model.py:141-181, same constructor (`batch_first` is accepted and ignored, as there), parameters (`real_lstm`, `imag_lstm`: one-layer
+    nn.LSTM holders, bidirectional when asked; `r_trans`, `i_trans` when `projection_dim` is given) and forward: [real, imag], each [T, B, input_size // 2],
+    -> [real_out, imag_out], each [T, B, projection_dim // 2] (without a projection hidden_size // 2, twice that when bidirectional: forward | reverse).
+    Each of the four LSTM calls starts from zero state; real_out = real_lstm(real) - imag_lstm(imag), imag_out = real_lstm(imag) + imag_lstm(real).
+    Differentiable in both inputs and every parameter (ComplexLSTM plan, csrc/plan_clstm.cpp); train and eval mode compute the same arithmetic.
+    As a child of DCCRN it is a parameter holder: the model owns the flat arenas and plans its recurrent block itself.  float32 cuda tensors."""
+
+    def __init__(self, input_size, hidden_size, projection_dim=None, bidirectional=False, batch_first=False):
+        super().__init__()
+        self.input_dim, self.rnn_units = input_size // 2, hidden_size // 2
+        self.bidirectional = bool(bidirectional)
+        self.real_lstm = nn.LSTM(self.input_dim, self.rnn_units, num_layers=1, bidirectional=self.bidirectional, batch_first=False)
+        self.imag_lstm = nn.LSTM(self.input_dim, self.rnn_units, num_layers=1, bidirectional=self.bidirectional, batch_first=False)
+        ndir = 2 if self.bidirectional else 1
+        if projection_dim is not None:
+            self.projection_dim = projection_dim // 2
+            self.r_trans = nn.Linear(self.rnn_units * ndir, self.projection_dim)
+            self.i_trans = nn.Linear(self.rnn_units * ndir, self.projection_dim)
+        else:
+            self.projection_dim = None
+        self._sizes = dict(input_size=int(input_size), hidden_size=int(hidden_size), projection_dim=None if projection_dim is None else int(projection_dim),
+                           bidirectional=self.bidirectional)
+        self.act_dtype = cfg.act_dtype
+        self._init_runtime_state()                   # (a DCCRN parent re-tags the parameters as its own afterwards)
+
+    def flatten_parameters(self):
+        pass                                         # tools_for_model.py:179-181: cuDNN weight compaction; the parameters here are views of one flat tensor already
+
+    def _clstm_runtime(self, B, T, device):
+        if not self._flat_ok(device):
+            self._flatten(device)
+        key = ("clstm", B, T, self.act_dtype, str(device))
+        rt = self._runtimes.get(key)
+        if rt is None:
+            # one training-capable plan for both modes: the layer has no mode-dependent arithmetic, and inside a larger network the input gradient is
+            # needed in eval mode too
+            plan = Plan(B, T, act_dtype=self.act_dtype, training=True, model="ComplexLSTM", clstm=self._sizes)
+            rt = _layer_arenas(self, plan, device)
+            self._runtimes[key] = rt
+        return rt
+
+    def forward(self, inputs):
+        if not isinstance(inputs, (list, tuple)) or len(inputs) != 2:
+            raise TypeError("sefd NavieComplexLSTM takes [real, imag], a list or tuple of two [T, B, input_size // 2] tensors; the reference's branch for a "
+                            f"bare tensor (torch.chunk(inputs, -1), tools_for_model.py:165-166) raises inside torch - got {type(inputs).__name__}")
+        real, imag = inputs
+        _check_frontend_input("NavieComplexLSTM", real, imag)
+        I, H, P = self.input_dim, self.rnn_units, self.projection_dim
+        if real.dim() != 3 or real.shape[2] != I or imag.shape != real.shape:
+            raise ValueError(f"NavieComplexLSTM takes two [T, B, {I}] tensors, got {tuple(real.shape)} and {tuple(imag.shape)}")
+        T, B = real.shape[0], real.shape[1]
+        rt = self._clstm_runtime(B, T, real.device)
+        # The [T, B, .] <-> batch-major permutes, the pad to roundup(I, 8) columns per part and the split into halves are element-wise torch at the
+        # plan's boundary, O(B T (I + H)) values beside the recurrences' O(B T H H) work; autograd carries the gradient through them.
+        pad = -I % 8
+        if pad:
+            real, imag = nn.functional.pad(real, (0, pad)), nn.functional.pad(imag, (0, pad))
+        x = torch.cat([real, imag], 2).permute(1, 0, 2).contiguous()
+        out = _CLSTMFunction.apply(self, rt, x, *[q for _, q in self._trainable()])
+        if P is not None:
+            halves = (out[..., :P], out[..., P:])
+        else:                                        # [D, B, T, real | imag] -> forward | reverse on the last axis
+            halves = tuple(torch.cat([out[d][..., p * H:(p + 1) * H] for d in range(out.shape[0])], -1) for p in (0, 1))
+        return [h.permute(1, 0, 2).contiguous() for h in halves]
 
 
 class cPReLU(nn.Module):

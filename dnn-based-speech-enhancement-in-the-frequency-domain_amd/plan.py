@@ -24,13 +24,13 @@ class Plan:
     def __init__(self, B, L, kernel_num=(32, 64, 128, 256, 256, 256), rnn_layers=2, rnn_units=256, win_len=400,
                  win_inc=100, fft_len=512, masking_mode="E", lstm="complex", skip_type=True, act_dtype="fp32",
                  kernel_size=5, training=True, model="DCCRN", fsn=None, bn_world=1, grad_buckets=1, use_cbn=False, win_type="hanning",
-                 cbn_sync=False, seq=None, feature_type="complex", conv=None, cbn=None):
+                 cbn_sync=False, seq=None, feature_type="complex", conv=None, cbn=None, clstm=None):
         self.lib = _lib.lib()
         if masking_mode not in MASK_MODES:
             raise NotImplementedError(f"masking_mode {masking_mode!r} is not on the HIP path yet")
         cfg = _lib.ModelConfig()
         cfg.model = {"DCCRN": 0, "CRN": 1, "STFT": 2, "FullSubNet": 3, "TorchSTFT": 4, "TorchISTFT": 5, "SequenceModel": 6, "ConvSTFT": 7,
-                     "ConviSTFT": 8, "ConvLayer": 9, "ComplexBatchNorm": 10}[model]
+                     "ConviSTFT": 8, "ConvLayer": 9, "ComplexBatchNorm": 10, "ComplexLSTM": 11}[model]
         cfg.B, cfg.L = int(B), int(L)
         if model == "FullSubNet":
             # L = number of STFT frames T; kernel_num carries (sb_neighbors, fb_neighbors, look_ahead, fb_hidden, sb_hidden,
@@ -72,8 +72,20 @@ class Plan:
             bits = lambda f: int(np.float32(f).view(np.int32))
             kernel_num = (v["num_features"], bits(v["eps"]), bits(v["momentum"]))
             self.cbn = v
+        if model == "ComplexLSTM":
+            # NavieComplexLSTM on its own (tools_for_model.py:141-181, csrc/plan_clstm.cpp): B = sequences, L = frames T; kernel_num carries the PER-PART sizes
+            #   (input_size // 2, hidden_size // 2, projection_dim // 2 or 0, bidirectional)
+            v = dict(input_size=2, hidden_size=16, projection_dim=None, bidirectional=False)
+            v.update(clstm or {})
+            for k in ("input_size", "hidden_size", "projection_dim"):
+                if v[k] is not None and v[k] % 2:
+                    raise ValueError(f"sefd plan: ComplexLSTM: {k} {v[k]} is odd: it has no real / imaginary halves")
+            if v["projection_dim"] is not None and v["projection_dim"] < 2:       # (0 in kernel_num means "no projection")
+                raise ValueError(f"sefd plan: ComplexLSTM: projection_dim / 2 must be at least 1, got projection_dim {v['projection_dim']} (None: no projection)")
+            kernel_num = (v["input_size"] // 2, v["hidden_size"] // 2, 0 if v["projection_dim"] is None else v["projection_dim"] // 2, 1 if v["bidirectional"] else 0)
+            self.clstm = v
         cfg.win_len, cfg.hop, cfg.fft_len = win_len, win_inc, fft_len
-        cfg.n_layers = len(kernel_num) if model not in ("FullSubNet", "SequenceModel", "ConvSTFT", "ConviSTFT", "ConvLayer", "ComplexBatchNorm") else 0
+        cfg.n_layers = len(kernel_num) if model not in ("FullSubNet", "SequenceModel", "ConvSTFT", "ConviSTFT", "ConvLayer", "ComplexBatchNorm", "ComplexLSTM") else 0
         for i, k in enumerate(kernel_num):
             cfg.kernel_num[i] = int(k)
         cfg.rnn_layers, cfg.rnn_units = rnn_layers, rnn_units

@@ -25,8 +25,8 @@ typedef struct sefd_plan sefd_plan;
 typedef struct sefd_model_config {
   int32_t model;          /* 0 DCCRN, 1 CRN, 2 ConvSTFT front end, 3 FullSubNet, 4 torch.stft front end, 5 torch.istft,
                              6 SequenceModel on its own, 7 ConvSTFT on its own, 8 ConviSTFT on its own, 9 one conv layer on its own (ConvLayer),
-                             10 ComplexBatchNorm on its own (see build_plan, csrc/plan.cpp) */
-  int32_t B, L;           /* batch, samples per clip (models 3, 6, 8 and 9: L = frames T; model 10: L = rows per batch item) */
+                             10 ComplexBatchNorm on its own, 11 NavieComplexLSTM on its own (ComplexLSTM) (see build_plan, csrc/plan.cpp) */
+  int32_t B, L;           /* batch, samples per clip (models 3, 6, 8, 9 and 11: L = frames T; model 10: L = rows per batch item) */
   int32_t win_len, hop, fft_len;
   int32_t n_layers;
   int32_t kernel_num[12]; /* cfg.dccrn_kernel_num; FullSubNet (model 3): sb/fb neighbours (each 0 .. 31), look_ahead, fb/sb hidden,
@@ -49,7 +49,12 @@ typedef struct sefd_model_config {
                              A geometry without an output bin or frame is refused with its numbers;
                              ComplexBatchNorm (model 10, tools_for_model.py:430-607; B = batch, L = S, the product of the trailing dimensions): [0] num_features (real + imaginary,
                              a multiple of 8), [1] eps, [2] momentum, both as float32 bit patterns.  x [B][C][S] -> y; grad_y -> grad_x; parameters Wrr Wri Wii Br Bi, buffers
-                             RMr RMi RVrr RVri RVii.  training = 1: batch statistics, running update; 0: running statistics, buffers untouched */
+                             RMr RMi RVrr RVri RVii.  training = 1: batch statistics, running update; 0: running statistics, buffers untouched;
+                             ComplexLSTM (model 11, tools_for_model.py:141-181, csrc/plan_clstm.cpp; B = sequences, L = frames T): [0] input size per part I, [1] hidden size per
+                             part H (a multiple of 8), [2] projection size per part P (0: no r_trans / i_trans), [3] bidirectional.  I/O, batch-major fp32, IP = roundup(I, 8):
+                             x [B][T][2 IP] (real | imaginary, pad columns zero) -> y [B][T][2 P] (real | imaginary); P = 0: the workspace buffer `hc` [D][B][T][2 H] in the
+                             activation dtype (direction, real | imaginary).  grad_y ([B][T][2 P], or [D][B][T][2 H]) -> grad_x [B][T][2 IP] and the flat gradients (parameters
+                             real_lstm.*, imag_lstm.*, r_trans.*, i_trans.* in torch's order, `_reverse` tensors behind a direction's forward ones) */
   int32_t rnn_layers, rnn_units;
   int32_t mask_mode;      /* 0 'E', 1 'C', 2 'R' (cfg.masking_mode) */
   int32_t lstm_complex;   /* cfg.lstm == 'complex' */
