@@ -2,12 +2,13 @@
 
 CPU: a DCCRN / CRN plan interpreted by the host simulator against the oracle - forward taps, the three outputs, running statistics and every
 parameter gradient - for any depth, channel tuple, front end and recurrent block the planner accepts (test_plan_hostsim.py, test_plan_configs_cpu.py).
-GPU: every launch of a plan against the host simulator from the same pre-op state (test_gpu_ops.py, test_gpu_plan_configs.py)."""
+GPU: every launch of a plan against the host simulator from the same pre-op state (test_gpu_ops.py, test_gpu_plan_configs.py, test_gpu_recurrence_edges.py,
+test_gpu_rungemm_persist.py, test_gpu_clstm.py): transport, change detection and the report here, the comparison rule in opcheck.py."""
 import os
 
-import numpy as np
 import torch
 
+import opcheck
 from oracle.dccrn import DCCRNConfig, dccrn_forward, dccrn_state_shapes, is_trainable
 from oracle.losses import main_loss
 from oracle.weights import formula_state_dict, test_signals as make_signals
@@ -251,21 +252,8 @@ def report_path(name):
     return os.path.join(d, name)
 
 
-def _typed(t_u8, dt):
-    return t_u8.view(torch.bfloat16 if dt == 1 else torch.float32)
-
-
-def ops_device_vs_sim(plan, P, model, B, L, dtype, per_element=False):
-    """Run every op of both phases of `plan` on the device and on the host simulator from the SAME pre-op state (so an error is localised to
-    one launch) and detect writes outside the regions the simulator's op changes.  P: {state_dict name: tensor}; model: DCCRN / DCCRN_CBN / CRN /
-    FullSubNet / SequenceModel (L = frames).  Bars, relative to the largest element of the region: fp32 buffers 1e-3, bf16 buffers 1.6e-2 (two bf16 ulps), fp32 state
-    of a bf16 recurrence op and the fp32 `.bnpart` sums of a bf16 GEMM 4e-3.  per_element (the cases with saturating gate biases only): a region
-    whose largest element exceeds 1 is measured per element, |device - simulator| <= tol * max(1, |simulator|) with the same tol - a bias of 100 in a
-    pre-activation slab or a cell state of 10 must not loosen the bar of every other element of its region.
-    Returns (report lines, the lines of the ops that miss)."""
-    dev = plan.alloc_arenas("cuda")
-    host = plan.alloc_arenas("cpu")
-    fill_params(plan, dev, P)
+def seed_inputs(plan, dev, P, model, B, L):
+    """The inputs and upstream gradients of the models this driver knows, from fixed seeds."""
     torch.manual_seed(1)
     if model == "FullSubNet":
         plan.io(dev, "mag", (B, 257, L)).copy_(torch.rand(B, 257, L) * 3)
@@ -286,31 +274,51 @@ def ops_device_vs_sim(plan, P, model, B, L, dtype, per_element=False):
         plan.io(dev, "grad_wav", (B, L)).copy_(torch.randn(B, L) * 1e-3)
         plan.io(dev, "grad_real", (B, plan.NF, plan.T)).copy_(torch.randn(B, plan.NF, plan.T) * 1e-4)
         plan.io(dev, "grad_imag", (B, plan.NF, plan.T)).copy_(torch.randn(B, plan.NF, plan.T) * 1e-4)
-    # region table: (arena, byte offset, bytes, dtype, name); GRAD / STATE arenas are single fp32 regions
-    regions = []
-    for name in plan.buffer_names():
-        a, off, nb, dt = plan.buffer(name)
-        regions.append((a, off, nb, dt, name))
-    regions.append((2, 0, plan.arena_bytes[2], 0, "A_GRAD"))
-    regions.append((3, 0, plan.arena_bytes[3], 0, "A_STATE"))
+
+
+def ops_device_vs_sim(plan, P, model, B, L, dtype, per_element=False, seed=None, report=None):
+    """Run every op of both phases of `plan` on the device and on the host simulator from the SAME pre-op state (so an error is localised to
+    one launch) and detect writes outside what the simulator's op changes.  P: {state_dict name: tensor}; model: DCCRN / DCCRN_CBN / CRN /
+    FullSubNet / SequenceModel (L = frames), seeded by seed_inputs; seed: a callable (plan, device arenas) that writes the plan's inputs and upstream
+    gradients instead (a plan seed_inputs does not know; model, B and L are then unused).
+    The comparison rule is opcheck.compare_op.  Bars: fp32 buffers 1e-3 and bf16 buffers 1.6e-2 (two bf16 ulps), relative to the largest element of the
+    BUFFER; every tensor of the gradient and the state arena on its own, 1e-3 relative to the largest element of the TENSOR (two named exceptions:
+    opcheck), and a byte the device changes in a tensor the simulator leaves alone is a stray write; the weight-gradient partial sums (`gradpart`) launch
+    by launch, 1e-3 relative to the largest partial sum the launch writes; fp32 state of a bf16 recurrence op and the fp32
+    `.bnpart` sums of a bf16 GEMM 4e-3.  per_element (the cases with saturating gate biases only): a buffer or tensor whose largest element exceeds 1 is
+    measured per element, |device - simulator| <= tol * max(1, |simulator|) with the same tol - a bias of 100 in a pre-activation slab or a cell state
+    of 10 must not loosen the bar of every other element of its region.
+    report: file name in the report directory (report_path) that receives the report lines followed by the per-tensor table (tensor, max|simulator|, worst err over the run).
+    Returns (report lines, the lines of the ops that miss)."""
+    dev = plan.alloc_arenas("cuda")
+    host = plan.alloc_arenas("cpu")
+    fill_params(plan, dev, P)
+    if seed is not None:
+        seed(plan, dev)
+    else:
+        seed_inputs(plan, dev, P, model, B, L)
+    # region table: (arena, byte offset, bytes, dtype, name); GRAD / STATE arenas are single fp32 regions here (change detection and transport) and
+    # are split per tensor by the comparator
+    table = opcheck.region_table(plan)
     check = [0, 2, 3, 5]
-    # The arenas stay on the device.  `host` mirrors the device state at every op boundary and `prev` is a second host copy
-    # of that state; after an op only the regions that the kernel or the simulator changed travel (device -> host), so the
+    # The arenas stay on the device.  `host` receives the simulator's op, `got` mirrors the device state and `prev` is the state in front of the op
+    # (all three equal at every op boundary); after an op only the regions that the kernel or the simulator changed travel (device -> host), so the
     # per-op cost is one device-side compare + one host-side memcmp instead of ten whole-arena copies.
     for a in range(6):
         host[a].copy_(dev[a])
     prev = {a: host[a].clone() for a in check}
-    by_arena = {a: [r for r in regions if r[0] == a and r[2] > 0] for a in check}
+    got = {a: host[a].clone() for a in check}
+    by_arena = {a: [(k, r) for k, r in enumerate(table.regions) if r[0] == a and r[2] > 0] for a in check}
     # 8-byte words: every region starts on a 256-byte boundary, so a word never straddles two regions
     w64 = {a: (dev[a].view(torch.uint8).numel() // 8) for a in check}
-    lo_idx = {a: torch.tensor([r[1] // 8 for r in by_arena[a]], device="cuda") for a in check}
-    hi_idx = {a: torch.tensor([min((r[1] + r[2] + 7) // 8, w64[a]) for r in by_arena[a]], device="cuda") for a in check}
+    lo_idx = {a: torch.tensor([r[1] // 8 for _, r in by_arena[a]], device="cuda") for a in check}
+    hi_idx = {a: torch.tensor([min((r[1] + r[2] + 7) // 8, w64[a]) for _, r in by_arena[a]], device="cuda") for a in check}
     # host side: which regions did the SIMULATOR change?  One vectorised pass per arena (words -> 256-byte blocks -> prefix sums; regions start on
     # 256-byte boundaries, so a block never straddles two regions) instead of one memcmp per region and op (28 000 torch.equal calls per case: half of the
     # suite's run time through round 5)
     nblk = {a: (w64[a] + 31) // 32 for a in check}
-    lo_blk = {a: torch.tensor([r[1] // 256 for r in by_arena[a]]) for a in check}
-    hi_blk = {a: torch.tensor([min((r[1] + r[2] + 255) // 256, nblk[a]) for r in by_arena[a]]) for a in check}
+    lo_blk = {a: torch.tensor([r[1] // 256 for _, r in by_arena[a]]) for a in check}
+    hi_blk = {a: torch.tensor([min((r[1] + r[2] + 255) // 256, nblk[a]) for _, r in by_arena[a]]) for a in check}
 
     def host_changed(a):
         h64 = host[a].view(torch.uint8)[:w64[a] * 8].view(torch.int64)
@@ -320,14 +328,14 @@ def ops_device_vs_sim(plan, P, model, B, L, dtype, per_element=False):
             ne = torch.cat([ne, torch.zeros(32 - ne.numel() % 32, dtype=torch.bool)])
         cs = torch.cat([torch.zeros(1, dtype=torch.int64), ne.view(-1, 32).any(1).to(torch.int64).cumsum(0)])
         return ((cs[hi_blk[a]] - cs[lo_blk[a]]) > 0).tolist()
-    lines, bad = [], []
+    lines, bad, log = [], [], opcheck.TensorLog()
     for phase in (PHASE_FWD, PHASE_BWD):
         kinds, tags = plan.op_kinds(phase)
         for i in range(plan.num_ops(phase)):
             dbefore = {a: dev[a].view(torch.uint8)[:w64[a] * 8].view(torch.int64).clone() for a in check}
             sim_run(plan, phase, host, i, i + 1)
             plan.run(phase, dev, 0, i, i + 1)
-            worst, nchg, stray, where = 0.0, 0, 0, ""
+            changed = []                                                              # [(region index, the device changed it)]
             for a in check:
                 if not by_arena[a]:
                     continue
@@ -335,39 +343,25 @@ def ops_device_vs_sim(plan, P, model, B, L, dtype, per_element=False):
                 cs = torch.cumsum(torch.cat([torch.zeros(1, dtype=torch.int32, device="cuda"), (d64 != dbefore[a]).to(torch.int32)]), 0)
                 dflags = ((cs[hi_idx[a]] - cs[lo_idx[a]]) > 0).cpu().tolist()        # the one synchronising read per arena
                 hflags = host_changed(a)
-                h8, p8, d8 = host[a].view(torch.uint8), prev[a].view(torch.uint8), dev[a].view(torch.uint8)
-                for (ra, off, nb, dt, name), dchg, hchg in zip(by_arena[a], dflags, hflags):
-                    if not (hchg or dchg):
-                        continue
-                    g8 = d8[off:off + nb].cpu() if dchg else p8[off:off + nb]
-                    if hchg:
-                        hv, gv = _typed(h8[off:off + nb], dt).double(), _typed(g8, dt).double()
-                        den = float(hv.abs().max())
-                        if per_element and den > 1.0:
-                            err = float(((hv - gv).abs() / hv.abs().clamp(min=1.0)).max())
-                        else:
-                            err = float((hv - gv).abs().max()) / (den if den > 0 else 1.0)
-                        if not np.isfinite(err):
-                            err = float("inf")
-                        tol = 1.6e-2 if dt == 1 else 1e-3
-                        if dt != 1 and dtype == "bf16" and int(kinds[i]) == 1 and name.endswith(".bnpart"):
-                            tol = 4e-3     # fp32 partial sums of the bf16 gradient tile this launch ALSO stores: where kernel and simulator round an
-                                           # element of that tile to different bf16 neighbours (allowed above: 2 ulps), a 128-row sum with cancellation
-                                           # moves by up to that ulp (seen 1.06e-3 of the region's largest sum)
-                        if dt != 1 and dtype == "bf16" and int(kinds[i]) in (9, 10):
-                            tol = 4e-3     # fp32 state of a bf16 recurrence (cell state, dh): h_t is rounded to bf16 every frame, and a
-                                           # rounding flip (one bf16 ulp = 4e-3 of h) between kernel and simulator feeds back into c
-                        nchg += hv.numel()
-                        if err / tol > worst:
-                            worst, where = err / tol, f"{name} err {err:.2e} tol {tol:.0e}"
-                    else:
-                        # stray write: the kernel changed bytes of a region the simulator did not touch
-                        stray += int((g8 != p8[off:off + nb]).sum())
-                    h8[off:off + nb].copy_(g8)                                        # both host copies := device state
+                g8, d8 = got[a].view(torch.uint8), dev[a].view(torch.uint8)
+                for (k, (ra, off, nb, dt, name)), dchg, hchg in zip(by_arena[a], dflags, hflags):
                     if dchg:
-                        p8[off:off + nb].copy_(g8)
-            lines.append(f"phase {phase} op {i:3d} {KIND.get(int(kinds[i]), str(int(kinds[i]))):16s} tag {int(tags[i]):4d} elems {nchg:9d} "
-                         f"err/tol {worst:.3e} stray {stray} {where}")
-            if not (worst < 1.0) or stray:
+                        g8[off:off + nb].copy_(d8[off:off + nb])
+                    if hchg or dchg:
+                        changed.append((k, dchg))
+            v = opcheck.compare_op(prev, host, got, table, int(kinds[i]), dtype, per_element, candidates=[k for k, _ in changed])
+            log.add(v)
+            for k, dchg in changed:
+                a, off, nb, dt, name = table.regions[k]
+                g8 = got[a].view(torch.uint8)[off:off + nb]
+                host[a].view(torch.uint8)[off:off + nb].copy_(g8)                     # all host copies := device state
+                if dchg:
+                    prev[a].view(torch.uint8)[off:off + nb].copy_(g8)
+            lines.append(f"phase {phase} op {i:3d} {KIND.get(int(kinds[i]), str(int(kinds[i]))):16s} tag {int(tags[i]):4d} elems {v.elems:9d} "
+                         f"err/tol {v.worst:.3e} stray {v.stray} {v.where}")
+            if not (v.worst < 1.0) or v.stray:
                 bad.append(lines[-1])
+    if report:
+        with open(report_path(report), "w") as f:
+            f.write("\n".join(lines + log.lines()) + "\n")
     return lines, bad

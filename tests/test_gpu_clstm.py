@@ -12,7 +12,7 @@ import torch
 
 import clstm_common as cc
 from clstm_common import CASES, TOL
-from plan_check import KIND, _typed, report_path
+from plan_check import ops_device_vs_sim, report_path
 from recurrence_cases import hot_biases
 from simutil import PHASE_BWD, PHASE_FWD, Plan, fill_params, sim_run
 from util import GOLDEN, knobs, load_golden
@@ -76,108 +76,13 @@ def test_module_against_reference_golden(name, dtype):
 
 
 # ------------------------------------------------------------------------------------------------ 2. every launch against the host simulator
-def ops_device_vs_sim(plan, P, x, gy, dtype, per_element=False):
-    """plan_check.ops_device_vs_sim for a ComplexLSTM plan.  That driver seeds the inputs of the models it knows and cannot take this one as it is, so
-    this is its body with the plan's own inputs (x, gy) in place of the seeding: every op of both phases on the device and on the host simulator from
-    the SAME pre-op state, with the same bars - relative to the largest element of a region fp32 buffers 1e-3, bf16 buffers 1.6e-2, the fp32 state of
-    a bf16 recurrence op 4e-3; per_element: regions whose largest element exceeds 1 per element - and the same stray-write detection.
-    Returns (report lines, the lines of the ops that miss)."""
-    dev = plan.alloc_arenas("cuda")
-    host = plan.alloc_arenas("cpu")
-    fill_params(plan, dev, P)
-    plan.io(dev, "x", tuple(x.shape)).copy_(x)
-    plan.io(dev, "grad_y", tuple(gy.shape)).copy_(gy)
-    # region table: (arena, byte offset, bytes, dtype, name); GRAD / STATE arenas are single fp32 regions
-    regions = []
-    for name in plan.buffer_names():
-        a, off, nb, dt = plan.buffer(name)
-        regions.append((a, off, nb, dt, name))
-    regions.append((2, 0, plan.arena_bytes[2], 0, "A_GRAD"))
-    regions.append((3, 0, plan.arena_bytes[3], 0, "A_STATE"))
-    check = [0, 2, 3, 5]
-    # The arenas stay on the device.  `host` mirrors the device state at every op boundary and `prev` is a second host copy
-    # of that state; after an op only the regions that the kernel or the simulator changed travel (device -> host), so the
-    # per-op cost is one device-side compare + one host-side memcmp instead of ten whole-arena copies.
-    for a in range(6):
-        host[a].copy_(dev[a])
-    prev = {a: host[a].clone() for a in check}
-    by_arena = {a: [r for r in regions if r[0] == a and r[2] > 0] for a in check}
-    # 8-byte words: every region starts on a 256-byte boundary, so a word never straddles two regions
-    w64 = {a: (dev[a].view(torch.uint8).numel() // 8) for a in check}
-    lo_idx = {a: torch.tensor([r[1] // 8 for r in by_arena[a]], device="cuda") for a in check}
-    hi_idx = {a: torch.tensor([min((r[1] + r[2] + 7) // 8, w64[a]) for r in by_arena[a]], device="cuda") for a in check}
-    # host side: which regions did the SIMULATOR change?  One vectorised pass per arena (words -> 256-byte blocks -> prefix sums; regions start on
-    # 256-byte boundaries, so a block never straddles two regions) instead of one memcmp per region and op (28 000 torch.equal calls per case: half of the
-    # suite's run time through round 5)
-    nblk = {a: (w64[a] + 31) // 32 for a in check}
-    lo_blk = {a: torch.tensor([r[1] // 256 for r in by_arena[a]]) for a in check}
-    hi_blk = {a: torch.tensor([min((r[1] + r[2] + 255) // 256, nblk[a]) for r in by_arena[a]]) for a in check}
-
-    def host_changed(a):
-        h64 = host[a].view(torch.uint8)[:w64[a] * 8].view(torch.int64)
-        p64 = prev[a].view(torch.uint8)[:w64[a] * 8].view(torch.int64)
-        ne = h64 != p64
-        if ne.numel() % 32:
-            ne = torch.cat([ne, torch.zeros(32 - ne.numel() % 32, dtype=torch.bool)])
-        cs = torch.cat([torch.zeros(1, dtype=torch.int64), ne.view(-1, 32).any(1).to(torch.int64).cumsum(0)])
-        return ((cs[hi_blk[a]] - cs[lo_blk[a]]) > 0).tolist()
-    lines, bad = [], []
-    for phase in (PHASE_FWD, PHASE_BWD):
-        kinds, tags = plan.op_kinds(phase)
-        for i in range(plan.num_ops(phase)):
-            dbefore = {a: dev[a].view(torch.uint8)[:w64[a] * 8].view(torch.int64).clone() for a in check}
-            sim_run(plan, phase, host, i, i + 1)
-            plan.run(phase, dev, 0, i, i + 1)
-            worst, nchg, stray, where = 0.0, 0, 0, ""
-            for a in check:
-                if not by_arena[a]:
-                    continue
-                d64 = dev[a].view(torch.uint8)[:w64[a] * 8].view(torch.int64)
-                cs = torch.cumsum(torch.cat([torch.zeros(1, dtype=torch.int32, device="cuda"), (d64 != dbefore[a]).to(torch.int32)]), 0)
-                dflags = ((cs[hi_idx[a]] - cs[lo_idx[a]]) > 0).cpu().tolist()        # the one synchronising read per arena
-                hflags = host_changed(a)
-                h8, p8, d8 = host[a].view(torch.uint8), prev[a].view(torch.uint8), dev[a].view(torch.uint8)
-                for (ra, off, nb, dt, name), dchg, hchg in zip(by_arena[a], dflags, hflags):
-                    if not (hchg or dchg):
-                        continue
-                    g8 = d8[off:off + nb].cpu() if dchg else p8[off:off + nb]
-                    if hchg:
-                        hv, gv = _typed(h8[off:off + nb], dt).double(), _typed(g8, dt).double()
-                        den = float(hv.abs().max())
-                        if per_element and den > 1.0:
-                            err = float(((hv - gv).abs() / hv.abs().clamp(min=1.0)).max())
-                        else:
-                            err = float((hv - gv).abs().max()) / (den if den > 0 else 1.0)
-                        if not np.isfinite(err):
-                            err = float("inf")
-                        tol = 1.6e-2 if dt == 1 else 1e-3
-                        if dt != 1 and dtype == "bf16" and int(kinds[i]) == 1 and name.endswith(".bnpart"):
-                            tol = 4e-3     # fp32 partial sums of the bf16 gradient tile this launch ALSO stores: where kernel and simulator round an
-                                           # element of that tile to different bf16 neighbours (allowed above: 2 ulps), a 128-row sum with cancellation
-                                           # moves by up to that ulp (seen 1.06e-3 of the region's largest sum)
-                        if dt != 1 and dtype == "bf16" and int(kinds[i]) in (9, 10):
-                            tol = 4e-3     # fp32 state of a bf16 recurrence (cell state, dh): h_t is rounded to bf16 every frame, and a
-                                           # rounding flip (one bf16 ulp = 4e-3 of h) between kernel and simulator feeds back into c
-                        nchg += hv.numel()
-                        if err / tol > worst:
-                            worst, where = err / tol, f"{name} err {err:.2e} tol {tol:.0e}"
-                    else:
-                        # stray write: the kernel changed bytes of a region the simulator did not touch
-                        stray += int((g8 != p8[off:off + nb]).sum())
-                    h8[off:off + nb].copy_(g8)                                        # both host copies := device state
-                    if dchg:
-                        p8[off:off + nb].copy_(g8)
-            lines.append(f"phase {phase} op {i:3d} {KIND.get(int(kinds[i]), str(int(kinds[i]))):16s} tag {int(tags[i]):4d} elems {nchg:9d} "
-                         f"err/tol {worst:.3e} stray {stray} {where}")
-            if not (worst < 1.0) or stray:
-                bad.append(lines[-1])
-    return lines, bad
-
-
 @pytest.mark.parametrize("hot", [False, True])
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("name", ["bi_h32", "bi_h128_proj", "bi_h192_proj"])
 def test_every_launch_against_host_simulator(name, dtype, hot):
+    """plan_check.ops_device_vs_sim with the plan's own inputs (x, grad_y): every op of both phases on the device and on the host simulator from the
+    SAME pre-op state, under the bars of tests/opcheck.py - buffers relative to the largest element of the buffer, every parameter gradient relative
+    to the largest element of that tensor; hot: its per-element rule - and its stray-write detection."""
     case = CASES[name]
     s = cc.sizes(case)
     P = cc.formula_params(case)
@@ -187,9 +92,13 @@ def test_every_launch_against_host_simulator(name, dtype, hot):
     xr, xi, gr, gi = cc.inputs(case)
     n = s["T"] * s["B"] * s["O"]
     plan = Plan(s["B"], s["T"], model="ComplexLSTM", clstm=cc.clstm_dict(case), act_dtype=dtype)
-    lines, bad = ops_device_vs_sim(plan, P, cc.to_plan_x(case, xr, xi), cc.to_plan_gy(case, gr / n, gi / n), dtype, per_element=hot)
-    with open(report_path(f"clstm_ops_{name}_{dtype}{'_hot' if hot else ''}.txt"), "w") as f:
-        f.write("\n".join(lines) + "\n")
+    x, gy = cc.to_plan_x(case, xr, xi), cc.to_plan_gy(case, gr / n, gi / n)
+
+    def seed(plan, dev):
+        plan.io(dev, "x", tuple(x.shape)).copy_(x)
+        plan.io(dev, "grad_y", tuple(gy.shape)).copy_(gy)
+    lines, bad = ops_device_vs_sim(plan, P, "ComplexLSTM", s["B"], s["T"], dtype, per_element=hot, seed=seed,
+                                   report=f"clstm_ops_{name}_{dtype}{'_hot' if hot else ''}.txt")
     assert not bad, "\n".join(bad)
     assert plan.status() == 0
     compared = lambda kind: [int(re.search(r"elems\s+(\d+)", l).group(1)) for l in lines if f" {kind} " in l]

@@ -9,6 +9,8 @@ import pytest
 import torch
 
 import convlayer_common as lc
+import opcheck
+from plan_check import report_path
 from simutil import ARENA_COUNT, PHASE_BWD, PHASE_FWD, Plan, fill_params, sim_run
 
 pytestmark = pytest.mark.gpu
@@ -106,14 +108,16 @@ def test_layout_kernel_alone(shape, dtype, tile):
             assert torch.equal(out, cl[:, t_off:, :, :C].float().permute(0, 3, 2, 1).contiguous()), (mode, t_off)
 
 
-def _ops_against_simulator(plan, values, inputs):
-    """Every op but the layout ops on the device and on the host simulator from the same pre-op state: fp32 buffers 1e-3, bf16 buffers 1.6e-2
-    (test_gpu_ops.test_every_op_against_host_simulator), relative to the largest element of the buffer.  The layout ops run on the device only."""
+def _ops_against_simulator(plan, values, inputs, report):
+    """Every op but the layout ops on the device and on the host simulator from the same pre-op state, under the rule of tests/opcheck.py: fp32
+    buffers 1e-3, bf16 buffers 1.6e-2 (test_gpu_ops.test_every_op_against_host_simulator), relative to the largest element of the buffer; every
+    parameter gradient and module buffer relative to the largest element of that tensor; no byte written where the simulator writes none.  The
+    layout ops run on the device only.  report: file in the report directory (plan_check.report_path) for the per-op lines and the per-tensor table."""
     dev = plan.alloc_arenas("cuda")
     fill_params(plan, dev, values)
-    regions = [plan.buffer(n) + (n,) for n in plan.buffer_names()] + [(2, 0, plan.arena_bytes[2], 0, "A_GRAD"), (3, 0, plan.arena_bytes[3], 0, "A_STATE")]
-    typed = lambda raw, dt: raw.view(torch.bfloat16 if dt == 1 else torch.float32).double()
-    n_checked = 0
+    table = opcheck.region_table(plan)
+    assert not any(r[4].endswith(".bnpart") for r in table.regions)      # no statistics sums in these plans: every fp32 bar here is 1e-3
+    n_checked, lines, log = 0, [], opcheck.TensorLog()
     for phase, (io, t) in ((PHASE_FWD, inputs[0]), (PHASE_BWD, inputs[1])):
         plan.io(dev, io, tuple(t.shape)).copy_(t)
         kinds = [int(k) for k in plan.op_kinds(phase)[0]]
@@ -126,19 +130,15 @@ def _ops_against_simulator(plan, values, inputs):
             if kind == OP_NCHW_CL:
                 continue
             sim_run(plan, phase, host, i, i + 1)
-            for a, off, nb, dt, name in regions:
-                h8, p8 = host[a].view(torch.uint8)[off:off + nb], prev[a].view(torch.uint8)[off:off + nb]
-                d8 = dev[a].view(torch.uint8)[off:off + nb].cpu()
-                if torch.equal(h8, p8):
-                    assert torch.equal(d8, p8), f"phase {phase} op {i} (kind {kind}) wrote {name}, which the simulator leaves alone"
-                    continue
-                hv, dv = typed(h8, dt), typed(d8, dt)
-                den = float(hv.abs().max())
-                err = float((hv - dv).abs().max()) / (den if den > 0 else 1.0)
-                tol = 1.6e-2 if dt == 1 else 1e-3
-                print(f"phase {phase} op {i} kind {kind} {name}: err {err:.2e} tol {tol:.0e}")
-                assert err <= tol, (phase, i, kind, name, err)
-                n_checked += 1
+            v = opcheck.compare_op(prev, host, [a.cpu() for a in dev], table, kind, "bf16")
+            log.add(v)
+            lines.append(f"phase {phase} op {i:3d} kind {kind:3d} elems {v.elems:9d} err/tol {v.worst:.3e} stray {v.stray} {v.where}")
+            print(lines[-1])
+            with open(report_path(report), "w") as f:
+                f.write("\n".join(lines + log.lines()) + "\n")
+            assert v.stray == 0, f"phase {phase} op {i} (kind {kind}) wrote {v.stray} bytes that the simulator leaves alone"
+            assert v.worst < 1.0, (phase, i, kind, v.where)
+            n_checked += len(v.rows)
     assert n_checked > 0
 
 
@@ -152,7 +152,7 @@ def test_bf16_conv_plans_op_by_op(name):
     m = lc.make_conv(models, name)
     lc.fill_(m, lc.SEED)
     inp = lc.conv_inputs(name)
-    _ops_against_simulator(plan, m.state_dict(), (("x", inp["x"]), ("grad_y", inp["cot"])))
+    _ops_against_simulator(plan, m.state_dict(), (("x", inp["x"]), ("grad_y", inp["cot"])), f"convlayer_ops_{name}.txt")
 
 
 def test_bf16_cbn_plan_op_by_op():
@@ -163,7 +163,7 @@ def test_bf16_cbn_plan_op_by_op():
     m = models.ComplexBatchNorm(C, momentum=momentum)
     lc.fill_(m, lc.SEED)
     inp = lc.cbn_inputs(name)
-    _ops_against_simulator(plan, m.state_dict(), (("x", inp["x"].reshape(lc.B, C, 30)), ("grad_y", inp["cot"].reshape(lc.B, C, 30))))
+    _ops_against_simulator(plan, m.state_dict(), (("x", inp["x"].reshape(lc.B, C, 30)), ("grad_y", inp["cot"].reshape(lc.B, C, 30))), f"convlayer_ops_{name}.txt")
 
 
 def test_composition_and_stamp():

@@ -37,9 +37,7 @@ def test_every_op_of_the_entry_against_host_simulator(e, dtype):
         okw = {k: v for k, v in kw.items() if k != "masking_mode"}
         P = formula_state_dict(dccrn_state_shapes(dccrn_config(kw.get("masking_mode", "E"), okw)))
     plan = Plan(e.B, e.L, **kw)
-    lines, bad = ops_device_vs_sim(plan, P, e.model, e.B, e.L, dtype)
-    with open(report_path(f"ops_report_cfg_{e.name}_{dtype}.txt"), "w") as f:
-        f.write("\n".join(lines) + "\n")
+    lines, bad = ops_device_vs_sim(plan, P, e.model, e.B, e.L, dtype, report=f"ops_report_cfg_{e.name}_{dtype}.txt")
     assert not bad, "\n".join(bad[:20])
 
 

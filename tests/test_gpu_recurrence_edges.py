@@ -66,10 +66,8 @@ def test_every_launch_of_a_sequence_model_plan_against_host_simulator(name, kn, 
     plan = Plan(c["B"], c["T"], model="SequenceModel", seq=seq_dict(c["seq"], c["I"], c["O"], c["H"], c["NL"], c["bi"]), act_dtype=c["dtype"])
     cluster = c["dtype"] == "bf16" and c["seq"] == "LSTM" and c["H"] > 128 and not kn
     assert lstm_launches(plan) == ([c["NL"], c["NL"]] if cluster else [0, 0])
-    lines, bad = ops_device_vs_sim(plan, P, "SequenceModel", c["B"], c["T"], c["dtype"], per_element=hot)
     tag = f"{name}{''.join('_' + k for k, _ in kn)}_{'hot' if hot else 'plain'}"
-    with open(report_path(f"ops_report_seq_{tag}.txt"), "w") as f:
-        f.write("\n".join(lines) + "\n")
+    lines, bad = ops_device_vs_sim(plan, P, "SequenceModel", c["B"], c["T"], c["dtype"], per_element=hot, report=f"ops_report_seq_{tag}.txt")
     fig = summarise(lines)
     record(f"seq_ops/{tag}", fig)
     assert not bad, "\n".join(bad[:20])
@@ -93,9 +91,7 @@ def test_every_launch_of_the_saturated_real_lstm_plan_against_host_simulator():
     kw = plan_kwargs(e, "bf16")
     P = rc.hot_biases(formula_state_dict(dccrn_state_shapes(dccrn_config("E", {k: v for k, v in kw.items() if k != "masking_mode"}))))
     assert sum(1 for k in P if "bias_ih_l" in k) == 2
-    lines, bad = ops_device_vs_sim(Plan(e.B, e.L, **kw), P, e.model, e.B, e.L, "bf16", per_element=True)
-    with open(report_path("ops_report_hot_lstm_real_bf16.txt"), "w") as f:
-        f.write("\n".join(lines) + "\n")
+    lines, bad = ops_device_vs_sim(Plan(e.B, e.L, **kw), P, e.model, e.B, e.L, "bf16", per_element=True, report="ops_report_hot_lstm_real_bf16.txt")
     fig = summarise(lines)
     record("plan_ops_hot/lstm_real_bf16", fig)
     assert not bad, "\n".join(bad[:20])
