@@ -202,7 +202,9 @@ bool rundirect_takes(const RunGemm& d);                                         
 bool launch_rungemm_persist(const RunGemm& d, const ArenaBases& ab, hipStream_t st); // persistent form of the 128-row LDS-DMA kernel (rungemm_persist.hip)
 int rungemm_persist_grid(const RunGemm& d);                                          // ... its grid; 0: `d` stays on rungemm_kernel
 // The kernel family launch_rungemm picks for a RUNGEMM descriptor under the knobs of the moment (sefd_plan_op_info reports it)
-enum RunFamily : int { kFamNone = 0, kFamEnc0 = 1, kFamCgemm256 = 2, kFamDirect = 3, kFamTiled = 4, kFamPersist = 5 };
+bool launch_thin_mask(const RunGemm& d, const ArenaBases& ab, hipStream_t st);       // frame-staged mask-layer conv and its input gradient (thin_mask.hip)
+int thin_mask_grid(const RunGemm& d);                                                // ... its grid; 0: `d` stays where it was
+enum RunFamily : int { kFamNone = 0, kFamEnc0 = 1, kFamCgemm256 = 2, kFamDirect = 3, kFamTiled = 4, kFamPersist = 5, kFamThinMask = 6 };
 int rungemm_family(const RunGemm& d);
 void launch_misc(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st);
