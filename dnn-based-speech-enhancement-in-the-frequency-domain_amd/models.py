@@ -1100,17 +1100,229 @@ class SequenceModel(_SefdModule):
 
 
 def _weight_init(m):
-    """BaseModel.weight_init (tools_for_model.py:1120-1184) for the module types a FullSubNet holds: Linear -> xavier_normal_ weight, normal_ bias;
-    LSTM / GRU -> orthogonal_ matrices, normal_ vectors.  `Module.apply` visits children first, as the reference's call does: same draws in the same order."""
-    if isinstance(m, nn.Linear):
+    """BaseModel.weight_init (tools_for_model.py:1120-1184), every module type its traversal names: Conv1d / ConvTranspose1d -> normal_ weight;
+    Conv2d, Conv3d and their transposes -> xavier_normal_ weight (bias, where there is one: normal_); BatchNorm1d-3d -> weight N(1, 0.02), bias 0;
+    Linear -> xavier_normal_ weight, normal_ bias; LSTM / GRU and their cells -> orthogonal_ matrices, normal_ vectors.  `Module.apply` visits
+    children first, as the reference's call does: same draws in the same order."""
+    if isinstance(m, (nn.Conv1d, nn.ConvTranspose1d)):
+        nn.init.normal_(m.weight.data)
+        if m.bias is not None:
+            nn.init.normal_(m.bias.data)
+    elif isinstance(m, (nn.Conv2d, nn.Conv3d, nn.ConvTranspose2d, nn.ConvTranspose3d)):
+        nn.init.xavier_normal_(m.weight.data)
+        if m.bias is not None:
+            nn.init.normal_(m.bias.data)
+    elif isinstance(m, (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d)):
+        nn.init.normal_(m.weight.data, mean=1, std=0.02)
+        nn.init.constant_(m.bias.data, 0)
+    elif isinstance(m, nn.Linear):
         nn.init.xavier_normal_(m.weight.data)
         nn.init.normal_(m.bias.data)
-    elif isinstance(m, (nn.LSTM, nn.GRU)):
+    elif isinstance(m, (nn.LSTM, nn.LSTMCell, nn.GRU, nn.GRUCell)):
         for param in m.parameters():
             if len(param.shape) >= 2:
                 nn.init.orthogonal_(param.data)
             else:
                 nn.init.normal_(param.data)
+
+
+# ------------------------------------------------------------------------------------------ BaseModel (tools_for_model.py:801-1185)
+BM_NORMS = ("offline_laplace_norm", "cumulative_laplace_norm", "offline_gaussian_norm", "cumulative_layer_norm",      # 0..3: plan.FSN_NORMS
+            "forgetting_norm", "sband_forgetting_norm", "hybrid_norm")                                                # 4..6: [B, F, T], sample length
+
+
+def _vp(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _bm_check(name, x, dim):
+    assert x.dim() == dim, f"The dim of input is {x.dim()}. It should be {dim} dim."
+    if not x.is_cuda:
+        raise RuntimeError(f"sefd BaseModel.{name} runs on the MI355X only (cuda tensors); there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise TypeError(f"sefd BaseModel.{name} takes float32 tensors, got {x.dtype}")
+
+
+def _bm_geometry(kind, shape):
+    """(rows, F, T) of include/sefd.h for a norm input: the cumulative pair has B * C rows, the offline pair one row of C * F * T values per
+    utterance (passed as F = C F T, T = 1), the recurrence norms B rows."""
+    if kind in (1, 3):
+        B, Cc, F, T = shape
+        g = (B * Cc, F, T)
+    elif kind in (0, 2):
+        B, Cc, F, T = shape
+        g = (B, Cc * F * T, 1)
+    else:
+        g = tuple(shape)
+    if max(g) >= 2 ** 31:
+        raise ValueError(f"sefd BaseModel norms: a dimension of {tuple(shape)} does not fit 32 bits")
+    return g
+
+
+def bm_ws_floats(kind, rows, F, T):
+    """sefd_norm_ws_floats in Python arithmetic (csrc/basemodel.hip norm_args / ws_layout; pinned to the C function by tests/test_basemodel_cpu.py), so that
+    the ops' fake implementations trace with symbolic shapes: the statistics, the partial sums and the backward's coefficients, in floats."""
+    if kind in (0, 2):
+        N = F * T
+        ns = min((N + 2047) // 2048, 256)
+        seg = ((N + ns - 1) // ns + 3) // 4 * 4
+        return 2 * rows * (2 + 2 * ((N + seg - 1) // seg) + 3)
+    fs = min((F + 31) // 32, 16)
+    fper = (F + fs - 1) // fs
+    fs = (F + fper - 1) // fper
+    return 2 * rows * T * (2 + fs * (2 if kind == 3 else 1) + 3)
+
+
+def bm_norm_forward(x, kind, sample_len):
+    """(y, ws) of sefd_norm_forward: x float32 cuda contiguous, 4-D (kinds 0..3) or 3-D (kinds 4..6)."""
+    L_ = _lib.lib()
+    rows, F, T = _bm_geometry(kind, x.shape)
+    n = L_.sefd_norm_ws_floats(kind, rows, F, T)
+    if n < 0:
+        raise RuntimeError(f"sefd {BM_NORMS[kind] if 0 <= kind < 7 else kind}: bad arguments for an input of shape {tuple(x.shape)}")
+    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    y = torch.empty_like(x)
+    rc = L_.sefd_norm_forward(kind, _vp(x), rows, F, T, int(sample_len), _vp(ws), _vp(y), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"sefd_norm_forward({BM_NORMS[kind]}, shape {tuple(x.shape)}, sample length {sample_len}) failed ({rc})")
+    return y, ws
+
+
+def bm_norm_backward(x, g, ws, kind, sample_len):
+    rows, F, T = _bm_geometry(kind, x.shape)
+    gx = torch.empty_like(x)
+    rc = _lib.lib().sefd_norm_backward(kind, _vp(x), _vp(g), rows, F, T, int(sample_len), _vp(ws), _vp(gx), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"sefd_norm_backward({BM_NORMS[kind]}, shape {tuple(x.shape)}) failed ({rc})")
+    return gx
+
+
+def bm_unfold_forward(x, n):
+    B, Cc, F, T = x.shape
+    if n >= F:
+        raise RuntimeError(f"sefd BaseModel.unfold: num_neighbor {n} must be less than the {F} frequencies (reflect padding)")
+    out = torch.empty((B, F, Cc, 2 * n + 1, T), dtype=torch.float32, device=x.device)
+    rc = _lib.lib().sefd_unfold_forward(_vp(x), B, Cc, F, T, n, _vp(out), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"sefd_unfold_forward(shape {tuple(x.shape)}, n {n}) failed ({rc})")
+    return out
+
+
+def bm_unfold_backward(g, shape, n):
+    B, Cc, F, T = shape
+    gx = torch.empty(tuple(shape), dtype=torch.float32, device=g.device)
+    rc = _lib.lib().sefd_unfold_backward(_vp(g), B, Cc, F, T, n, _vp(gx), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"sefd_unfold_backward(shape {tuple(shape)}, n {n}) failed ({rc})")
+    return gx
+
+
+class _BMNormFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kind, sample_len):
+        x = x.contiguous()
+        y, ws = bm_norm_forward(x, kind, sample_len)
+        ctx.kind, ctx.sample_len = kind, sample_len
+        ctx.save_for_backward(x, ws)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, ws = ctx.saved_tensors
+        return bm_norm_backward(x, g.float().contiguous(), ws, ctx.kind, ctx.sample_len), None, None
+
+
+class _BMUnfoldFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, n):
+        ctx.n, ctx.shape = n, tuple(x.shape)
+        return bm_unfold_forward(x.contiguous(), n)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return bm_unfold_backward(g.float().contiguous(), ctx.shape, ctx.n), None
+
+
+def _bm_norm(name, x, dim, sample_len=1):
+    _bm_check(name, x, dim)
+    return _BMNormFunction.apply(x, BM_NORMS.index(name), int(sample_len))
+
+
+class BaseModel(nn.Module):
+    """The reference's BaseModel (tools_for_model.py:801-1185), the class a FullSubNet variant subclasses: `unfold` and the seven norms are
+    static methods on float32 cuda tensors in the reference's layout, each one autograd Function over the streaming kernels of csrc/basemodel.hip
+    (sefd_norm_* / sefd_unfold_* of include/sefd.h); it saves the input and the per-frame statistics, there is no double backward.  Inside
+    `FullSubNet` the fused plan does this work on its own buffers (csrc/fsn.hip) and does not come through here."""
+
+    def __init__(self):
+        super().__init__()
+
+    @staticmethod
+    def unfold(input, num_neighbor):
+        """[B, C, F, T] -> [B, F, C, 2 num_neighbor + 1, T]: the sub-band units along the reflect-padded frequency axis (:806-837)."""
+        _bm_check("unfold", input, 4)
+        return _BMUnfoldFunction.apply(input, max(int(num_neighbor), 0))
+
+    @staticmethod
+    def _reduce_complexity_separately(sub_band_input, full_band_output, device):
+        """tools_for_model.py:840-878: out = cat over i = 0, 1, 2 of cat(sub_band_input, full_band_output; unit axis)[i B/3 : (i+1) B/3, i+1 : F-1 : 3].
+        A pure gather: index selects in torch, autograd carries it."""
+        both = torch.cat([sub_band_input, full_band_output], dim=-2)          # [B, F, C, K_sb + K_fb, T]
+        B, F = both.shape[:2]
+        third = B // 3
+        thirds = []
+        for i in range(3):
+            rows = torch.arange(i * third, (i + 1) * third, device=device)
+            bins = torch.arange(i + 1, F - 1, 3, device=device)                 # the padded first and last frequencies are never taken
+            thirds.append(both.index_select(0, rows).index_select(1, bins))
+        return torch.cat(thirds, dim=0)
+
+    @staticmethod
+    def sband_forgetting_norm(input, train_sample_length):
+        """[B, F, T] (:881-913): forgetting_norm whose frames past the sample length follow the single bin F // 2 - 1."""
+        return _bm_norm("sband_forgetting_norm", input, 3, train_sample_length)
+
+    @staticmethod
+    def forgetting_norm(input, sample_length_in_training):
+        """[B, F, T] (:916-948): x / (mu_t + 1e-10), mu_t the exponentially forgetting mean of the frame means."""
+        return _bm_norm("forgetting_norm", input, 3, sample_length_in_training)
+
+    @staticmethod
+    def hybrid_norm(input, sample_length_in_training=192):
+        """[B, F, T] (:951-994): the forgetting mean for the first sample_length_in_training frames, the cumulative mean afterwards."""
+        return _bm_norm("hybrid_norm", input, 3, sample_length_in_training)
+
+    @staticmethod
+    def offline_laplace_norm(input):
+        """[B, C, F, T] (:997-1011): x / (utterance mean + 1e-5)."""
+        return _bm_norm("offline_laplace_norm", input, 4)
+
+    @staticmethod
+    def cumulative_laplace_norm(input):
+        """[B, C, F, T] (:1014-1044): x / (cumulative mean up to the frame + eps)."""
+        return _bm_norm("cumulative_laplace_norm", input, 4)
+
+    @staticmethod
+    def offline_gaussian_norm(input):
+        """[B, C, F, T] (:1047-1061): (x - utterance mean) / (unbiased utterance std + 1e-5)."""
+        return _bm_norm("offline_gaussian_norm", input, 4)
+
+    @staticmethod
+    def cumulative_layer_norm(input):
+        """[B, C, F, T] (:1064-1104): (x - cumulative mean) / sqrt(cumulative variance + eps)."""
+        return _bm_norm("cumulative_layer_norm", input, 4)
+
+    def norm_wrapper(self, norm_type: str):
+        if norm_type in BM_NORMS[:4]:
+            return getattr(self, norm_type)
+        raise NotImplementedError("You must set up a type of Norm. "
+                                  "e.g. offline_laplace_norm, cumulative_laplace_norm, forgetting_norm, etc.")
+
+    def weight_init(self, m):
+        """Usage: model.apply(model.weight_init) (:1120-1184)."""
+        _weight_init(m)
 
 
 class _FSNFunction(torch.autograd.Function):
@@ -1137,8 +1349,8 @@ class _FSNFunction(torch.autograd.Function):
         return (None, None, None) + tuple(flat[off:off + n].view(shape) for (off, n, shape) in ctx.owner._param_slices)
 
 
-class FullSubNet(_SefdModule):
-    """Same constructor as the reference (models.py:569-581)."""
+class FullSubNet(_SefdModule, BaseModel):
+    """Same constructor as the reference (models.py:569-581); a BaseModel, as there (its unfold and norms run inside the fused plan)."""
 
     def __init__(self, sb_num_neighbors=cfg.sb_num_neighbors, fb_num_neighbors=cfg.fb_num_neighbors, num_freqs=cfg.num_freqs,
                  look_ahead=cfg.look_ahead, sequence_model=cfg.sequence_model, fb_output_activate_function=cfg.fb_output_activate_function,

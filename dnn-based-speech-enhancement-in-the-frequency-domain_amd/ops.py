@@ -3,7 +3,7 @@
 The reference has no native op surface (everything below `models.py` is ATen / cuDNN); north_star asks for the HIP path
 "exposed as PyTorch-ROCm custom ops".  Each op below is a thin, allocation-explicit wrapper of ONE C-ABI entry point of include/sefd.h
 (same argument meaning, cuda tensors only, current HIP stream), registered with a fake (meta) implementation so that it traces, and - for
-the losses - with a registered backward.  The nn.Module mirrors (`models.py`, `tools_for_loss.py`) call the same C entry points directly
+the losses and BaseModel's norms and unfold - with a registered backward.  The nn.Module mirrors (`models.py`, `tools_for_loss.py`) call the same C entry points directly
 through ctypes (no dispatcher hop inside the fused train step); `tests/test_gpu_ops.py::test_torch_library_ops` pins op == mirror.
 
     torch.ops.sefd.loss(kind, est, tgt)                       scalar loss of tools_for_loss.py:17-94 (kind 0 MSE, 1 SDR, 2 SI-SNR, 3 SI-SDR),
@@ -12,6 +12,8 @@ through ctypes (no dispatcher hop inside the fused train step); `tests/test_gpu_
     torch.ops.sefd.mix_snr(speech, bank, start, snr_db, q)   generate_noisy_data.py:46-67 on the GPU
     torch.ops.sefd.composite_measures(clean, enh, fs)         composite.m frame analysis: [B, 3] fp64 (trimmed LLR, trimmed WSS, segSNR)
     torch.ops.sefd.plan_run(handle, phase, arenas)            one phase (0 forward, 1 backward) of a planned model: sefd_plan_run
+    torch.ops.sefd.basemodel_norm(x, kind, sample_len)        BaseModel's seven norms (tools_for_model.py:881-1104) by number, differentiable w.r.t. x
+    torch.ops.sefd.unfold(x, n)                               BaseModel.unfold (tools_for_model.py:806-837), differentiable w.r.t. x
 """
 import ctypes as C
 from typing import List, Tuple
@@ -121,6 +123,105 @@ def _loss_bwd(ctx, g):
 
 
 loss.register_autograd(_loss_bwd, setup_context=_loss_setup)
+
+
+# ---------------------------------------------------------------------------------------------- BaseModel norms and unfold
+def _bm_need(x, dims):
+    _need_cuda(x)
+    if x.dtype != torch.float32:
+        raise TypeError(f"sefd BaseModel ops take float32 tensors, got {x.dtype}")
+    if x.dim() not in dims:
+        raise ValueError(f"sefd BaseModel ops: a {x.dim()}-D input where {' or '.join(map(str, dims))}-D is expected")
+
+
+@torch.library.custom_op("sefd::basemodel_norm_forward", mutates_args=())
+def basemodel_norm_forward(x: torch.Tensor, kind: int, sample_len: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(y, workspace) of sefd_norm_forward: x fp32 contiguous, [B, C, F, T] for kinds 0..3, [B, F, T] for kinds 4..6."""
+    from .models import bm_norm_forward
+    _bm_need(x, (4,) if kind < 4 else (3,))
+    return bm_norm_forward(x, kind, sample_len)
+
+
+@basemodel_norm_forward.register_fake
+def _(x, kind, sample_len):
+    from .models import _bm_geometry, bm_ws_floats
+    return torch.empty_like(x), x.new_empty((bm_ws_floats(kind, *_bm_geometry(kind, x.shape)),))      # Python arithmetic: symbolic shapes trace
+
+
+@torch.library.custom_op("sefd::basemodel_norm_backward", mutates_args=("ws",))
+def basemodel_norm_backward(x: torch.Tensor, grad_y: torch.Tensor, ws: torch.Tensor, kind: int, sample_len: int) -> torch.Tensor:
+    """grad_x of sefd_norm_backward; ws is the forward's, whose scratch part this call overwrites (the statistics stay).  Because of that write,
+    autograd's version check refuses a SECOND backward through a retained graph of sefd::basemodel_norm; the BaseModel methods take one."""
+    from .models import bm_norm_backward
+    _bm_need(x, (4,) if kind < 4 else (3,))
+    _need_cuda(grad_y, ws)
+    return bm_norm_backward(x, grad_y, ws, kind, sample_len)
+
+
+@basemodel_norm_backward.register_fake
+def _(x, grad_y, ws, kind, sample_len):
+    return torch.empty_like(x)
+
+
+def _bm_norm_setup(ctx, inputs, output):
+    x, ctx.kind, ctx.sample_len = inputs
+    ctx.save_for_backward(x, output[1])                 # the input and the forward's statistics: nothing is recomputed
+
+
+def _bm_norm_bwd(ctx, gy, gws):
+    x, ws = ctx.saved_tensors
+    return basemodel_norm_backward(x, gy.contiguous(), ws, ctx.kind, ctx.sample_len), None, None
+
+
+basemodel_norm_forward.register_autograd(_bm_norm_bwd, setup_context=_bm_norm_setup)
+
+# sefd::basemodel_norm(x, kind, sample_len) -> y is the forward op's first output: a composite, so autograd and tracing see the op underneath
+torch.library.define("sefd::basemodel_norm", "(Tensor x, int kind, int sample_len) -> Tensor")
+
+
+@torch.library.impl("sefd::basemodel_norm", "CompositeImplicitAutograd")
+def basemodel_norm(x, kind, sample_len):
+    """BaseModel's norms (tools_for_model.py:881-1104) by number: 0..3 = offline_laplace, cumulative_laplace, offline_gaussian, cumulative_layer on
+    [B, C, F, T]; 4..6 = forgetting, sband_forgetting, hybrid on [B, F, T] with their training sample length."""
+    return torch.ops.sefd.basemodel_norm_forward(x.contiguous(), kind, sample_len)[0]
+
+
+@torch.library.custom_op("sefd::unfold", mutates_args=())
+def unfold(x: torch.Tensor, n: int) -> torch.Tensor:
+    """BaseModel.unfold (tools_for_model.py:806-837): [B, C, F, T] -> [B, F, C, 2 n + 1, T] (n < 1: the permute)."""
+    from .models import bm_unfold_forward
+    _bm_need(x, (4,))
+    return bm_unfold_forward(x.contiguous(), max(n, 0))
+
+
+@unfold.register_fake
+def _(x, n):
+    B, Cc, F, T = x.shape
+    return x.new_empty((B, F, Cc, 2 * max(n, 0) + 1, T))
+
+
+@torch.library.custom_op("sefd::unfold_backward", mutates_args=())
+def unfold_backward(grad_out: torch.Tensor, B: int, Cc: int, F: int, T: int, n: int) -> torch.Tensor:
+    from .models import bm_unfold_backward
+    _bm_need(grad_out, (5,))
+    return bm_unfold_backward(grad_out.contiguous(), (B, Cc, F, T), max(n, 0))
+
+
+@unfold_backward.register_fake
+def _(grad_out, B, Cc, F, T, n):
+    return grad_out.new_empty((B, Cc, F, T))
+
+
+def _unfold_setup(ctx, inputs, output):
+    x, ctx.n = inputs
+    ctx.shape = tuple(x.shape)
+
+
+def _unfold_bwd(ctx, g):
+    return unfold_backward(g, *ctx.shape, ctx.n), None
+
+
+unfold.register_autograd(_unfold_bwd, setup_context=_unfold_setup)
 
 
 # ---------------------------------------------------------------------------------------------- Adam

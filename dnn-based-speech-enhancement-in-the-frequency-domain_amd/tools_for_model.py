@@ -15,9 +15,9 @@ def __getattr__(name):
     if name == "SequenceModel":
         from .models import SequenceModel
         return SequenceModel
-    # tools_for_model.py:36-112 and 126-607, defined in models.py beside the models that hold them
+    # tools_for_model.py:36-112, 126-607 and 801-1185, defined in models.py beside the models that hold them
     if name in ("ConvSTFT", "ConviSTFT", "ComplexConv2d", "ComplexConvTranspose2d", "RealConv2d", "RealConvTranspose2d", "ComplexBatchNorm", "cPReLU",
-                "complex_cat", "NavieComplexLSTM"):
+                "complex_cat", "NavieComplexLSTM", "BaseModel"):
         from . import models
         return getattr(models, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -222,6 +222,37 @@ int64_t sefd_composite_ws_bytes(int32_t B, int32_t L, int32_t fs);
 int32_t sefd_composite_frames(const float* clean, const float* enhanced, int32_t B, int32_t L, int32_t fs, void* ws, double* out, void* stream);
 int32_t sefd_fsn_targets(const float* noisy_c64, const float* clean_c64, int64_t n, float* mag, float* phase, float* cirm, void* stream);
 
+/* ---- BaseModel on its own (tools_for_model.py:801-1185): the seven norms and `unfold` on tensors in the reference's layout ----------
+ * x, y, grad_y, grad_x: fp32 device, [rows][F][T] with the frames contiguous.  A row is what the statistics are taken over per frame:
+ * B * C rows for cumulative_laplace_norm / cumulative_layer_norm on [B, C, F, T], B rows for the three recurrence norms on [B, F, T].  The two
+ * offline norms take one mean (and std) over ALL F * T values of a row: pass rows = B, F = C * F * T, T = 1 (any split of the row's
+ * values into F x T gives the same result).
+ * kind: SEFD_NORM_* below; 0..3 in the order of FSN_NORMS.  sample_len: the recurrence norms' training sample length (ignored by kinds 0..3).
+ * ws: sefd_norm_ws_floats(kind, rows, F, T) floats of device memory, 8-byte aligned, owned by ONE forward / backward pair.  It begins with the
+ * per-(row, frame) statistics as doubles { mean, std }, which forward writes and backward reads (with the same x); the rest is the pair's scratch (the
+ * per-frame partial sums of each pass, then the backward's per-frame coefficients), and the backward OVERWRITES it - its ws is const for the statistics only.
+ * The tensors need 4-byte alignment only: frames are moved 16 bytes at a time when T % 4 == 0 (offline: F * T % 4 == 0) and every tensor pointer is
+ * 16-byte aligned, element by element otherwise (same values).
+ * Both return -1, and launch nothing, for a kind out of range, a size below 1, sample_len < 1 (kinds 4..6), sband_forgetting with F < 2,
+ * offline_gaussian with fewer than 2 values per row, a NULL or misaligned pointer; -2: launch failure.  They only enqueue: no allocation,
+ * no synchronisation, no state inside the library.  No atomics: results are bit-identical from run to run, and a row's result depends on that row alone. */
+#define SEFD_NORM_OFFLINE_LAPLACE 0
+#define SEFD_NORM_CUMULATIVE_LAPLACE 1
+#define SEFD_NORM_OFFLINE_GAUSSIAN 2
+#define SEFD_NORM_CUMULATIVE_LAYER 3
+#define SEFD_NORM_FORGETTING 4
+#define SEFD_NORM_SBAND_FORGETTING 5
+#define SEFD_NORM_HYBRID 6
+int64_t sefd_norm_ws_floats(int32_t kind, int32_t rows, int32_t F, int32_t T);
+int32_t sefd_norm_forward(int32_t kind, const float* x, int32_t rows, int32_t F, int32_t T, int32_t sample_len, float* ws, float* y, void* stream);
+int32_t sefd_norm_backward(int32_t kind, const float* x, const float* grad_y, int32_t rows, int32_t F, int32_t T, int32_t sample_len,
+                           const float* ws, float* grad_x, void* stream);
+/* BaseModel.unfold: x [B][C][F][T] -> out [B][F][C][2 n + 1][T], out[b, f, c, k, :] = x[b, c, reflect(f - n + k), :] (F.pad(mode="reflect"));
+ * n = 0 is the permute to [B][F][C][1][T].  backward: grad_x[b, c, j, :] = the sum, in a fixed order, of the grad_out rows that read bin j.
+ * -1, and nothing launched, for n < 0 or n >= F (torch's reflect pad refuses it), a size below 1 or a NULL pointer. */
+int32_t sefd_unfold_forward(const float* x, int32_t B, int32_t C, int32_t F, int32_t T, int32_t n, float* out, void* stream);
+int32_t sefd_unfold_backward(const float* grad_out, int32_t B, int32_t C, int32_t F, int32_t T, int32_t n, float* grad_x, void* stream);
+
 /* ---- Adam (torch.optim.Adam defaults, train_interface.py:59) on flat fp32 buffers ------------------
  * step is 1-based. */
 int32_t sefd_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int32_t step,
