@@ -211,6 +211,8 @@ void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st);
 void launch_istft_fft(const IstftFft& d, const ArenaBases& ab, hipStream_t st);
 void launch_ifft_ola(const IfftOla& d, const ArenaBases& ab, hipStream_t st);   // fused inverse FFT + overlap-add (stft_fft.hip)
 void launch_specconv(const SpecConv& d, const ArenaBases& ab, hipStream_t st);   // ConvSTFT / ConviSTFT spectrum conversions (stft_fft.hip)
+void launch_ola_fold(const Ola& d, const ArenaBases& ab, hipStream_t st);        // torch.stft's backward: overlap-add + reflect-padding adjoint (stft_fft.hip)
+void launch_specout_adj(const SpecOut& d, const ArenaBases& ab, hipStream_t st); // torch.istft's backward: weighted spectrum out (stft_fft.hip)
 void launch_nchw_cl(const NchwCl& d, const ArenaBases& ab, hipStream_t st);      // reference layout <-> channels-last (layout.hip)
 void launch_fsn(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_bn(const Op& op, const ArenaBases& ab, hipStream_t st);

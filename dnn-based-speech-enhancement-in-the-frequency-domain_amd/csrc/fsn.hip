@@ -580,6 +580,8 @@ void launch_fsn(const Op& op, const ArenaBases& ab, hipStream_t st) {
     case OP_STFT_FFT: launch_stft_fft(op.fft, ab, st); break;
     case OP_ISTFT_FFT: launch_istft_fft(op.ifft, ab, st); break;
     case OP_IFFT_OLA: launch_ifft_ola(op.iola, ab, st); break;
+    case OP_OLA_FOLD: launch_ola_fold(op.ola, ab, st); break;
+    case OP_SPECOUT_ADJ: launch_specout_adj(op.so, ab, st); break;
     case OP_REFLECTPAD: hipLaunchKernelGGL(reflectpad_kernel, dim3(gridn((int64_t)op.rpad.B * (op.rpad.L + 2 * op.rpad.pad))), dim3(256), 0, st, op.rpad, ab); break;
     case OP_CELL_FWD:
       if (op.cell.kind == 1) hipLaunchKernelGGL(gru_fwd_kernel, dim3(gridn(op.cell.rows * op.cell.H)), dim3(256), 0, st, op.cell, ab);
@@ -660,7 +662,58 @@ __global__ __launch_bounds__(256) void fsn_targets_kernel(const float* noisy, co
   }
 }
 
+// Backward of fsn_targets_kernel: one pass over the interleaved complex inputs; the gradient of noisy and / or clean (whichever pointer is given),
+// each element written once.  Cotangents that are null count as zero.
+//   mag, phase:  d re = g_m re / m - g_p (im / m) / m,  d im = g_m im / m + g_p (re / m) / m;  m == 0: both 0 (torch: NaN) - ConvSTFT's rule
+//   cIRM: h_e = g_e f'(v_e), f'(v) = K C 2 e^{-Cv} / (1 + e^{-Cv})^2 (0 on the clamped arm v <= -100), v = (a, b) / den, a = nr cr + ni ci, b = nr ci - ni cr:
+//     d cr = (h_0 nr - h_1 ni) / den, d ci = (h_0 ni + h_1 nr) / den,
+//     d nr = (h_0 cr + h_1 ci) / den - 2 nr (h_0 v_0 + h_1 v_1) / den,  d ni = (h_0 ci - h_1 cr) / den - 2 ni (h_0 v_0 + h_1 v_1) / den
+__global__ __launch_bounds__(256) void fsn_targets_bwd_kernel(const float* noisy, const float* clean, int64_t n, const float* g_mag, const float* g_phase,
+                                                              const float* g_cirm, float* d_noisy, float* d_clean) {
+  GSL(i, n) {
+    const float nr = noisy[2 * i], ni = noisy[2 * i + 1];
+    float dr = 0.f, di = 0.f;
+    if (g_mag || g_phase) {
+      const float m = sqrtf(nr * nr + ni * ni);
+      if (m != 0.f) {
+        const float gm = g_mag ? g_mag[i] : 0.f, gp = g_phase ? g_phase[i] : 0.f;
+        dr = gm * nr / m - gp * (ni / m) / m;
+        di = gm * ni / m + gp * (nr / m) / m;
+      }
+    }
+    if (g_cirm) {
+      const float cr = clean[2 * i], ci = clean[2 * i + 1];
+      const float den = nr * nr + ni * ni + 1.1920929e-07f;          // np.finfo(np.float32).eps
+      const float v[2] = {(nr * cr + ni * ci) / den, (nr * ci - ni * cr) / den};
+      float h[2];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const float ex = expf(-0.1f * v[e]), q = 1.f + ex;
+        h[e] = v[e] <= -100.f ? 0.f : g_cirm[2 * i + e] * (2.f * ex / (q * q));       // K C = 1
+      }
+      if (d_clean) {
+        d_clean[2 * i] = (h[0] * nr - h[1] * ni) / den;
+        d_clean[2 * i + 1] = (h[0] * ni + h[1] * nr) / den;
+      }
+      const float hv = 2.f * (h[0] * v[0] + h[1] * v[1]);
+      dr += (h[0] * cr + h[1] * ci - nr * hv) / den;
+      di += (h[0] * ci - h[1] * cr - ni * hv) / den;
+    }
+    if (d_noisy) { d_noisy[2 * i] = dr; d_noisy[2 * i + 1] = di; }
+  }
+}
+
 }  // namespace sefd
+
+extern "C" int32_t sefd_fsn_targets_backward(const float* noisy_c64, const float* clean_c64, int64_t n, const float* g_mag, const float* g_phase, const float* g_cirm,
+                                             float* d_noisy, float* d_clean, void* stream) {
+  using namespace sefd;
+  if (!noisy_c64 || n < 0 || (g_cirm && !clean_c64) || (d_clean && !g_cirm) || (!d_noisy && !d_clean)) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(fsn_targets_bwd_kernel, dim3(gridn(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), noisy_c64, clean_c64, n, g_mag, g_phase, g_cirm,
+                     d_noisy, d_clean);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
 
 extern "C" int32_t sefd_fsn_targets(const float* noisy_c64, const float* clean_c64, int64_t n, float* mag, float* phase, float* cirm, void* stream) {
   using namespace sefd;

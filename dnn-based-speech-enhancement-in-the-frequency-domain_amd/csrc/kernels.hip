@@ -762,6 +762,10 @@ __global__ void ola_bwd_kernel(const Ola d, const ArenaBases ab) {
     const int s = p - d.trim;
     if (d.noclamp == 2) {                                   // ConviSTFT on its own: no clamp, every sample passes its gradient
       if (s >= 0 && s < (d.Lout > 0 ? d.Lout : d.L)) v = dwav[b * d.L + s] / (coff[p] + 1e-8f);
+    } else if (d.noclamp == 1) {                            // torch.istft's backward: the forward divided by the envelope alone; wav is not read
+      // coff here: [2][Lp], the float64 reciprocal of the envelope as a float pair (hi, lo) - one rounding where a division by the rounded envelope
+      // has two, and at a clip's last taps the quotient is all there is to a frame's gradient
+      if (s >= 0 && s < (d.Lout > 0 ? d.Lout : d.L)) { const float g = dwav[b * d.L + s]; v = fmaf(g, coff[p], g * coff[Lp + p]); }
     } else if (s >= 0 && s < (d.Lout > 0 ? d.Lout : d.L)) {
       const float w = wav[b * d.L + s];
       // clamp_ passes the gradient where the un-clamped value lies in [-1, 1]; a clamped sample equals +-1 exactly

@@ -196,6 +196,8 @@ void finish_plan(Builder& b, Plan* P, int64_t nparam, int64_t nstate) {
 }
 
 Plan* build_plan(const ModelConfig& cfg) {
+  if (cfg.model == 13) return build_torchistft_adj_plan(cfg);
+  if (cfg.model == 12) return build_torchstft_adj_plan(cfg);
   if (cfg.model == 11) return build_clstm_plan(cfg);
   if (cfg.model == 10) return build_cbn_plan(cfg);
   if (cfg.model == 9) return build_convlayer_plan(cfg);

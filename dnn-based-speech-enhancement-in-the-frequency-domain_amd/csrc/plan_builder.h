@@ -937,6 +937,8 @@ Plan* build_fsn_plan(const ModelConfig& cfg);
 Plan* build_seq_plan(const ModelConfig& cfg);
 Plan* build_torchstft_plan(const ModelConfig& cfg);
 Plan* build_torchistft_plan(const ModelConfig& cfg);
+Plan* build_torchstft_adj_plan(const ModelConfig& cfg);
+Plan* build_torchistft_adj_plan(const ModelConfig& cfg);
 Plan* build_convstft_plan(const ModelConfig& cfg);
 Plan* build_convistft_plan(const ModelConfig& cfg);
 Plan* build_convlayer_plan(const ModelConfig& cfg);

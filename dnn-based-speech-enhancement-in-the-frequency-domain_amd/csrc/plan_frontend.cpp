@@ -311,6 +311,135 @@ Plan* build_convstft_plan(const ModelConfig& cfg) {
   return P;
 }
 
+// =================================================================================================================
+// The backward passes of models 4 and 5 as plans of their own (models 12 and 13), so that the forward plans keep their bytes.  Neither reads
+// anything a forward run left behind: any number of forwards of one shape may precede their backwards.  fft_len == 512 only (the FFT frame
+// kernels); whatever the forward twin refuses is refused here with the twin's sentence.
+namespace {
+
+// The forward twin's verdict on this geometry: its error sentence ("" = accepted) and its frame count.
+std::string twin_verdict(const ModelConfig& cfg, int model, int* T) {
+  ModelConfig fc = cfg;
+  fc.model = model;
+  Plan* F = model == 4 ? build_torchstft_plan(fc) : build_torchistft_plan(fc);
+  const std::string err = F->error;
+  *T = F->T;
+  delete F;
+  return err;
+}
+
+std::vector<double> centred_hann(int W, int NFFT) {
+  std::vector<double> win(NFFT, 0.0);
+  const int left = (NFFT - W) / 2;
+  for (int j = 0; j < W; ++j) win[left + j] = 0.5 - 0.5 * std::cos(2.0 * kPi * j / W);
+  return win;
+}
+
+}  // namespace
+
+// torch.stft's backward (model 12).  io.grad_spec [B][NF][T][2], the complex cotangent g = dL/dRe + i dL/dIm -> io.grad_wav [B][L]:
+//   dxp[q] = sum_t w[j] Re sum_{k <= N/2} g[k, t] e^{+2 pi i k j / N},  j = q - t hop      (no half weights, no 1 / N, no normaliser)
+//   dx[i]  = dxp[i + pad] + [1 <= i <= pad] dxp[pad - i] + [L-1-pad <= i <= L-2] dxp[pad + 2 (L-1) - i]
+// The transform is the inverse-FFT frame kernel with a zero correction table and the window times 256 (as ConvSTFT's backward); the overlap-add
+// and the fold are one gather (OP_OLA_FOLD): no [B][L + N] intermediate.
+Plan* build_torchstft_adj_plan(const ModelConfig& cfg) {
+  Plan* P = new Plan();
+  P->cfg = cfg;
+  const int B = cfg.B, L = cfg.L, W = cfg.win_len, hop = cfg.hop, NFFT = cfg.fft_len;
+  const int NF = NFFT / 2 + 1, SW = (NF + 1) * 2;
+  P->NF = NF;
+  int T = 0;
+  P->error = twin_verdict(cfg, 4, &T);
+  if (!P->error.empty()) return P;
+  if (NFFT != 512) {
+    P->error = "torch.stft backward plan: fft_len " + std::to_string(NFFT) + " is not 512, the only size the inverse-FFT frame kernel is built for";
+    return P;
+  }
+  P->T = T;
+  Builder b;
+  b.P = P;
+  b.c = cfg;
+  const int64_t BT = (int64_t)B * T;
+  Ptr io_gs = b.io("grad_spec", BT * NF * 2);
+  Ptr io_gw = b.io("grad_wav", (int64_t)B * L);
+  Ptr gspec = b.ws("gspec", BT * SW, DT_F32);
+  Ptr frames = b.ws("frames", BT * NFFT, DT_F32);
+  SpecOut so;
+  std::memset(&so, 0, sizeof(so));
+  so.est = gspec; so.out_real = io_gs; so.out_imag = b.none(); so.B = B; so.T = T; so.NF = NF; so.mode = 3; so.accumulate = 0;
+  b.push(P->fwd, OP_SPECOUT_BWD, 1).so = so;
+  fft_twiddles(b);
+  {
+    std::vector<double> w256 = centred_hann(W, NFFT);
+    for (double& v : w256) v *= 256.0;                        // the frame kernel's fixed 1/256 (a power of two: exact)
+    std::vector<float> zc(4 * 257, 0.f);
+    Op& op = b.push(P->fwd, OP_ISTFT_FFT, 2);
+    op.ifft.est = gspec; op.ifft.frames = frames; op.ifft.tw = b.fft_tw; op.ifft.win = b.win512(w256);
+    op.ifft.corr = b.cst(zc.data(), (int64_t)zc.size() * 4); op.ifft.nframes = BT; op.ifft.W = NFFT;
+  }
+  Ola ola;
+  std::memset(&ola, 0, sizeof(ola));
+  ola.frames = frames; ola.wav = io_gw; ola.coff = ola.dwav = ola.dpad = b.none();
+  ola.B = B; ola.T = T; ola.L = L; ola.win = NFFT; ola.hop = hop; ola.trim = NFFT / 2; ola.noclamp = 1;
+  b.push(P->fwd, OP_OLA_FOLD, 3).ola = ola;
+  finish_plan(b, P, 0, 0);
+  return P;
+}
+
+// torch.istft's backward (model 13).  io.grad_wav [B][L] -> io.grad_spec [B][NF][T][2], of y[p] = sum_t frames[t][p + pad - t hop] / env[p + pad]:
+//   gy'[q] = gy[q - pad] / env[q] on the covered samples (zero past Ola::Lout),  gframes[t][j] = w[j] gy'[t hop + j],
+//   gX[k, t] = (c_k / N) sum_j gframes[t][j] e^{-2 pi i k j / N},  c_0 = c_{N/2} = 1, else 2;  Im gX = 0 at DC and Nyquist
+// OP_OLA_BWD (noclamp = 1) + OP_STFT_FFT, the pair DCCRN's backward runs, then the weighted transpose (OP_SPECOUT_ADJ).
+Plan* build_torchistft_adj_plan(const ModelConfig& cfg) {
+  Plan* P = new Plan();
+  P->cfg = cfg;
+  const int B = cfg.B, L = cfg.L, W = cfg.win_len, hop = cfg.hop, NFFT = cfg.fft_len;
+  const int pad = NFFT / 2, NF = NFFT / 2 + 1, SW = (NF + 1) * 2;
+  P->NF = NF;
+  int T = 0;
+  P->error = twin_verdict(cfg, 5, &T);                        // fft_len != 512, the window, the hop, and the envelope test
+  if (!P->error.empty()) return P;
+  P->T = T;
+  Builder b;
+  b.P = P;
+  b.c = cfg;
+  const int64_t BT = (int64_t)B * T;
+  const int Lp = (T - 1) * hop + NFFT;
+  const int Lcov = std::min(L, Lp - pad);
+  Ptr io_gw = b.io("grad_wav", (int64_t)B * L);
+  Ptr io_gs = b.io("grad_spec", BT * NF * 2);
+  Ptr dpad = b.ws("dpad", (int64_t)B * Lp, DT_F32);
+  Ptr dest = b.ws("dest", BT * SW, DT_F32);
+  const std::vector<double> win = centred_hann(W, NFFT);
+  std::vector<double> env64(Lp, 0.0);                         // the forward plan's table
+  for (int t = 0; t < T; ++t)
+    for (int j = 0; j < NFFT; ++j) env64[t * hop + j] += win[j] * win[j];
+  std::vector<float> renv(2 * (size_t)Lp, 0.f);               // 1 / env as a float pair (hi | lo): OLA_BWD with noclamp = 1 (sefd_desc.h)
+  for (int p = pad; p < pad + Lcov; ++p) {                    // the twin has checked these: env > 1e-11
+    const double r = 1.0 / env64[p];
+    renv[p] = (float)r;
+    renv[(size_t)Lp + p] = (float)(r - (double)renv[p]);
+  }
+  Ola ola;
+  std::memset(&ola, 0, sizeof(ola));
+  ola.frames = b.none(); ola.wav = io_gw; ola.coff = b.cst(renv.data(), (int64_t)renv.size() * 4); ola.dwav = io_gw; ola.dpad = dpad;
+  ola.B = B; ola.T = T; ola.L = L; ola.win = NFFT; ola.hop = hop; ola.trim = pad; ola.noclamp = 1; ola.Lout = Lcov < L ? Lcov : 0;
+  b.push(P->fwd, OP_OLA_BWD, 1).ola = ola;
+  fft_twiddles(b);
+  {
+    Op& op = b.push(P->fwd, OP_STFT_FFT, 2);
+    op.fft.src = dpad; op.fft.spec = dest; op.fft.tw = b.fft_tw; op.fft.win = b.win512(win);
+    op.fft.B = B; op.fft.L = Lp; op.fft.T = T; op.fft.hop = hop; op.fft.off = 0; op.fft.lp_dt = 0;
+    op.fft.corr = b.none(); op.fft.scale = 1.f; op.fft.lp = b.none(); op.fft.pair = b.fft_pair();
+  }
+  SpecOut so;
+  std::memset(&so, 0, sizeof(so));
+  so.est = dest; so.out_real = io_gs; so.out_imag = b.none(); so.B = B; so.T = T; so.NF = NF; so.mode = 3;
+  b.push(P->fwd, OP_SPECOUT_ADJ, 3).so = so;
+  finish_plan(b, P, 0, 0);
+  return P;
+}
+
 // ConviSTFT: cfg.L = frames T (the FullSubNet convention).  io.in [B][2 NF][T] ('complex') or io.mags, io.phase [B][NF][T] -> io.wav [B][Lout],
 // Lout = (T - 1) hop + win_len - 2 (win_len - hop); no clamp, division by coff + 1e-8.  Backward io.grad_wav -> io.grad_in / io.grad_mags, io.grad_phase.
 Plan* build_convistft_plan(const ModelConfig& cfg) {

@@ -311,12 +311,18 @@ struct Ola {
   int32_t noclamp, Lout;       // noclamp = 1: torch.istft semantics (no clamp_(-1, 1), division by coff alone); the ConviSTFT path of DCCRN / CRN clamps
                                // noclamp = 2: ConviSTFT on its own (tools_for_model.py:101-110): no clamp, but coff + 1e-8; its backward does not read wav
                                // Lout > 0: ConviSTFT returned only the first Lout < L samples (the hop does not tile the clip): the rest of wav is 0, its dwav unread
+  // OLA_BWD with noclamp = 1 (torch.istft's backward): dpad = dwav / envelope, no clamp, wav unread; coff is then fp32 [2][Lp]: 1 / envelope (float64) as a pair hi | lo.
+  // OP_OLA_FOLD (torch.stft's backward) reads frames [B][T][win], writes wav [B][L] and uses B, T, L, win, hop, trim = pad = win / 2 only:
+  //   wav[b][i] = S(i + pad) + [1 <= i <= pad] S(pad - i) + [L-1-pad <= i <= L-2] S(pad + 2 (L-1) - i),   S(q) = sum_t frames[b][t][q - t hop]
+  // over the frames that reach q, in frame order: the overlap-add of the padded clip and the adjoint of its reflect padding, one write per sample.
 };
 
 // est spec [B][T][NF+1][2] (fp32, slot layout above) <-> reference layout out_real/out_imag [B][NF][T] fp32
 // mode 1: out_real = |est| (magnitude of the pairs, CRN target_mags) ; mode 2: est is a plain [B*T][NF] fp32 array -> out_real
 // mode 3: out_real receives the interleaved complex tensor [B][NF][T][2] (memory image of torch.complex64 [B, NF, T]);
 //         SPECOUT_BWD with mode 3 is the inverse copy [B][NF][T][2] -> est (the input side of the torch.istft plan)
+// OP_SPECOUT_ADJ: out_real [B][NF][T][2] = (c_k / (2 (NF - 1))) est, c_0 = c_{NF-1} = 1, else 2; the imaginary parts of bins 0 and NF - 1 are 0
+//         (the adjoint of irfft's half-spectrum input, as torch's backward gives it)
 struct SpecOut {
   Ptr est, out_real, out_imag; // forward: est -> out_*   ; backward: dest += d(out_*)
   int32_t B, T, NF, accumulate;
@@ -483,6 +489,8 @@ enum OpKind : int32_t {
   OP_IFFT_OLA,                       // fused inverse FFT + window + overlap-add (struct IfftOla)
   OP_SPECCONV,                       // ConvSTFT / ConviSTFT spectrum conversions (struct SpecConv)
   OP_NCHW_CL,                        // reference layout <-> channels-last at a stand-alone layer's boundary (struct NchwCl)
+  OP_OLA_FOLD,                       // torch.stft's backward: overlap-add + the adjoint of the reflect padding in one gather (struct Ola, see there)
+  OP_SPECOUT_ADJ,                    // torch.istft's backward: slot layout -> [B][NF][T][2] with the irfft adjoint's bin weights (struct SpecOut, see there)
 };
 
 constexpr int kOpHold = 2;     // Op::join of a lane-1 op

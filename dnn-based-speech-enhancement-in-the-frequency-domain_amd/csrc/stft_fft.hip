@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include "sefd_desc.h"
 #include "tuning.h"
+#include <algorithm>
 #include <cstdlib>
 #include "dev_common.h"
 
@@ -470,6 +471,74 @@ __global__ __launch_bounds__(256) void specconv_kernel(const SpecConv d, const A
   }
 }
 
+// torch.stft's backward behind the inverse-FFT frame kernel (struct Ola, OP_OLA_FOLD): the overlap-add of the padded clip's gradient and the adjoint of
+// its reflect padding in one gather.  One thread per output sample i of a clip (consecutive lanes: consecutive samples, so the frames buffer is read in
+// whole lines at the sample's own position and, mirrored, at its reflections): it sums its own position i + pad over the frames that reach it, then
+// the left mirror pad - i (1 <= i <= pad), then the right mirror pad + 2 (L - 1) - i (L - 1 - pad <= i <= L - 2), each in frame order, and writes once.
+// No [B][L + 2 pad] intermediate, no atomics: bit-identical run to run, and a clip's gradient does not depend on the rest of the batch.
+__device__ __forceinline__ float ola_fold_sum(const float* f, int q, int T, int win, int hop) {
+  int t1 = q / hop; if (t1 > T - 1) t1 = T - 1;
+  int t0 = (q - win + hop) / hop; if (q - win + 1 <= 0) t0 = 0;
+  float s = 0.f;
+  for (int t = t0; t <= t1; ++t) s += f[(int64_t)t * win + (q - t * hop)];      // 0 <= q - t hop < win for every t in [t0, t1]
+  return s;
+}
+__global__ __launch_bounds__(256) void ola_fold_kernel(const Ola d, const ArenaBases ab) {
+  const float* fr = reinterpret_cast<const float*>(rp(ab, d.frames));
+  float* out = reinterpret_cast<float*>(rp(ab, d.wav));
+  const int pad = d.trim, L = d.L;
+  const int64_t n = (int64_t)d.B * L;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / L;
+    const int s = (int)(i - b * L);
+    const float* f = fr + b * d.T * d.win;
+    float v = ola_fold_sum(f, s + pad, d.T, d.win, d.hop);
+    if (s >= 1 && s <= pad) v += ola_fold_sum(f, pad - s, d.T, d.win, d.hop);
+    if (s >= L - 1 - pad && s <= L - 2) v += ola_fold_sum(f, pad + 2 * (L - 1) - s, d.T, d.win, d.hop);
+    out[i] = v;
+  }
+}
+
+// torch.istft's backward, last step (struct SpecOut, OP_SPECOUT_ADJ): the analysis transform of the windowed waveform gradient in the slot layout ->
+// the [B][NF][T][2] image of the complex gradient, times c_k / N (c = 1 at DC and Nyquist, else 2: the adjoint of irfft reading half a spectrum);
+// the imaginary parts of DC and Nyquist are 0.  Both weights are powers of two at N = 512: the scaling is exact.  Tiles as specout_fwd_kernel.
+__global__ __launch_bounds__(256) void specout_adj_kernel(const SpecOut d, const ArenaBases ab) {
+  __shared__ float tr[32][33], ti[32][33];
+  const float* est = reinterpret_cast<const float*>(rp(ab, d.est));
+  float* out = reinterpret_cast<float*>(rp(ab, d.out_real));
+  const int NS = d.NF + 1;
+  const int b = blockIdx.z, t0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int r = ty; r < 32; r += 8) {
+    const int t = t0 + r, k = k0 + tx;
+    float vr = 0.f, vi = 0.f;
+    if (t < d.T && k < d.NF) {
+      const int64_t o = (((int64_t)b * d.T + t) * NS + k + 1) * 2;
+      vr = est[o]; vi = est[o + 1];
+    }
+    tr[r][tx] = vr; ti[r][tx] = vi;
+  }
+  __syncthreads();
+  const float w1 = 1.f / (float)(2 * (d.NF - 1));
+  for (int r = ty; r < 32; r += 8) {
+    const int k = k0 + r, t = t0 + tx;
+    if (t < d.T && k < d.NF) {
+      const bool edge = k == 0 || k == d.NF - 1;
+      const float w = edge ? w1 : 2.f * w1;
+      const int64_t o = ((int64_t)b * d.NF + k) * d.T + t;
+      out[2 * o] = w * tr[tx][r];
+      out[2 * o + 1] = edge ? 0.f : w * ti[tx][r];
+    }
+  }
+}
+
+void launch_ola_fold(const Ola& d, const ArenaBases& ab, hipStream_t st) {
+  const int64_t blocks = ((int64_t)d.B * d.L + 255) / 256;
+  hipLaunchKernelGGL(ola_fold_kernel, dim3((unsigned)std::min<int64_t>(blocks, 16384)), dim3(256), 0, st, d, ab);
+}
+void launch_specout_adj(const SpecOut& d, const ArenaBases& ab, hipStream_t st) {
+  hipLaunchKernelGGL(specout_adj_kernel, dim3((d.T + 31) / 32, (d.NF + 31) / 32, d.B), dim3(256), 0, st, d, ab);
+}
 void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st) {
   const int64_t frames = (int64_t)d.B * d.T;
   if (!d.pair) { hipLaunchKernelGGL(stft_fft_single_kernel, dim3((unsigned)((frames + 4 * kStftFPW - 1) / (4 * kStftFPW))), dim3(256), 0, st, d, ab); return; }

@@ -30,7 +30,7 @@ class Plan:
             raise NotImplementedError(f"masking_mode {masking_mode!r} is not on the HIP path yet")
         cfg = _lib.ModelConfig()
         cfg.model = {"DCCRN": 0, "CRN": 1, "STFT": 2, "FullSubNet": 3, "TorchSTFT": 4, "TorchISTFT": 5, "SequenceModel": 6, "ConvSTFT": 7,
-                     "ConviSTFT": 8, "ConvLayer": 9, "ComplexBatchNorm": 10, "ComplexLSTM": 11}[model]
+                     "ConviSTFT": 8, "ConvLayer": 9, "ComplexBatchNorm": 10, "ComplexLSTM": 11, "TorchSTFTAdj": 12, "TorchISTFTAdj": 13}[model]
         cfg.B, cfg.L = int(B), int(L)
         if model == "FullSubNet":
             # L = number of STFT frames T; kernel_num carries (sb_neighbors, fb_neighbors, look_ahead, fb_hidden, sb_hidden,

@@ -25,7 +25,9 @@ typedef struct sefd_plan sefd_plan;
 typedef struct sefd_model_config {
   int32_t model;          /* 0 DCCRN, 1 CRN, 2 ConvSTFT front end, 3 FullSubNet, 4 torch.stft front end, 5 torch.istft,
                              6 SequenceModel on its own, 7 ConvSTFT on its own, 8 ConviSTFT on its own, 9 one conv layer on its own (ConvLayer),
-                             10 ComplexBatchNorm on its own, 11 NavieComplexLSTM on its own (ComplexLSTM) (see build_plan, csrc/plan.cpp) */
+                             10 ComplexBatchNorm on its own, 11 NavieComplexLSTM on its own (ComplexLSTM), 12 the backward of model 4 (TorchSTFTAdj:
+                             grad_spec [B][NF][T][2] -> grad_wav [B][L]), 13 the backward of model 5 (TorchISTFTAdj: grad_wav [B][L] -> grad_spec [B][NF][T][2]);
+                             both fft_len 512 only, forward phase only, nothing saved from models 4 / 5 (see build_plan, csrc/plan.cpp) */
   int32_t B, L;           /* batch, samples per clip (models 3, 6, 8, 9 and 11: L = frames T; model 10: L = rows per batch item) */
   int32_t win_len, hop, fft_len;
   int32_t n_layers;
@@ -221,6 +223,13 @@ int32_t sefd_mix_snr(const float* speech, const float* noise, const int64_t* noi
 int64_t sefd_composite_ws_bytes(int32_t B, int32_t L, int32_t fs);
 int32_t sefd_composite_frames(const float* clean, const float* enhanced, int32_t B, int32_t L, int32_t fs, void* ws, double* out, void* stream);
 int32_t sefd_fsn_targets(const float* noisy_c64, const float* clean_c64, int64_t n, float* mag, float* phase, float* cirm, void* stream);
+/* Its backward, one pass over the interleaved complex inputs (fp32 device, n bins).  Cotangents g_mag, g_phase [n] and g_cirm [n][2], each NULL for
+ * "no gradient"; d_noisy / d_clean [n][2] (NULL: not wanted) receive (dL/dre, dL/dim) of that argument and are written once, no accumulation.
+ *   mag, phase: d re = g_m re / m - g_p im / m^2, d im = g_m im / m + g_p re / m^2; both 0 where m == 0 (torch: NaN)
+ *   cIRM: through K (1 - e^{-C v}) / (1 + e^{-C v}), K = 10, C = 0.1 (derivative 0 on the clamped arm v <= -100) and the ratio with den = |noisy|^2 + float32 eps.
+ * clean_c64 may be NULL when g_cirm is.  Returns 0, -1 bad arguments, -2 launch failure. */
+int32_t sefd_fsn_targets_backward(const float* noisy_c64, const float* clean_c64, int64_t n, const float* g_mag, const float* g_phase, const float* g_cirm,
+                                  float* d_noisy, float* d_clean, void* stream);
 
 /* ---- BaseModel on its own (tools_for_model.py:801-1185): the seven norms and `unfold` on tensors in the reference's layout ----------
  * x, y, grad_y, grad_x: fp32 device, [rows][F][T] with the frames contiguous.  A row is what the statistics are taken over per frame:
