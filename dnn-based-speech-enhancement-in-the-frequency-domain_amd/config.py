@@ -69,6 +69,10 @@ num_groups_in_drop_band = 2
 act_dtype = 'fp32'          # 'fp32' (parity mode) or 'bf16' (storage + MFMA operand dtype, fp32 accumulate)
 pmsqe_power = False         # False (default) = the reference's literal call chain: PMSQE is handed transforms.mag(...) magnitudes (tools_for_loss.py:267-269).
                             # True = opt-in build-side variant on power spectra |X|^2 (the published loss's own definition; +0.29 PESQ on the synthetic held-out set, profiles/r02_heldout_eval.json)
+optimizer = 'Adam'          # 'Adam' or 'AdamW' (decoupled weight decay): what train_interface.run builds when it is handed no optimizer
+weight_decay = 0.0          # non-zero: on the weights only, through model.get_params(weight_decay) (models.py:289); biases stay without decay
+amsgrad = False
+max_grad_norm = None        # a number: global-norm gradient clipping inside the fused step (torch.nn.utils.clip_grad_norm_'s formula)
 train_data_path = None      # [N, 2, L] .npy files of (noisy, clean) pairs; dataloader.py:63-71 has placeholder paths
 valid_data_path = None
 test_data_path = None

@@ -85,13 +85,23 @@ class _NullWriter:
     def log_wav(self, *a): pass
 
 
+def build_optimizer(model):
+    """The default optimizer from cfg.optimizer / learning_rate / weight_decay / amsgrad / max_grad_norm; with the defaults it is the reference's
+    `Adam(model.parameters(), lr=cfg.learning_rate)` (train_interface.py:59)."""
+    from . import optim
+    if cfg.optimizer not in ("Adam", "AdamW"):
+        raise ValueError(f"cfg.optimizer {cfg.optimizer!r}: 'Adam' or 'AdamW'")
+    params = model.get_params(cfg.weight_decay) if cfg.weight_decay != 0 else model.parameters()
+    return getattr(optim, cfg.optimizer)(params, lr=cfg.learning_rate, weight_decay=cfg.weight_decay, amsgrad=cfg.amsgrad,
+                                         max_grad_norm=cfg.max_grad_norm)
+
+
 def run(train_loader, validation_loader, model=None, optimizer=None, writer=None, DEVICE=None, exchange=None, rank=0, scorers="default",
         max_epochs=None):
     """The reference's main program: returns (model, optimizer, mse_vali_total, dir_to_save)."""
-    from .optim import Adam
     DEVICE = torch.device(DEVICE or cfg.DEVICE)
     model = model if model is not None else build_model(DEVICE)
-    optimizer = optimizer if optimizer is not None else Adam(model.parameters(), lr=cfg.learning_rate)
+    optimizer = optimizer if optimizer is not None else build_optimizer(model)
     total_params = calculate_total_params(model)
     trainer, estimator = select_trainer_and_estimator()
     max_epochs = max_epochs or cfg.max_epochs

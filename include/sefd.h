@@ -286,6 +286,52 @@ int32_t sefd_adam_step_guarded_dp(float* param, const float* grad, float* exp_av
 int32_t sefd_plan_status(const sefd_plan* p, int32_t clear);
 int32_t sefd_plan_status_set(const sefd_plan* p);
 
+/* ---- Grouped optimizer step (optim.hip): Adam / AdamW with weight decay, amsgrad, parameter groups, frozen parameters and global-norm clipping
+ * on the same flat fp32 buffers.  sefd_adam_step* above stay what they are; this is the path for every configuration they cannot express.
+ *
+ * Chunk table.  The part of the flat buffer that is updated is listed as chunks of at most SEFD_OPTIM_CHUNK elements: [begin, begin + count) in group
+ * `group`.  No chunk crosses a parameter tensor's boundary (a tensor is cut into full chunks and one remainder), chunks do not overlap, and an
+ * element that no chunk covers is frozen: its value and moments are neither read nor written.  The caller builds the table once, keeps one copy in
+ * host memory (the entry points check it against n on every call: a wrong table is refused, not launched) and one in device memory (what the kernels
+ * read).  One workgroup of 256 threads takes one chunk - up to 8192 chunks every chunk has its own workgroup, beyond that a workgroup goes on to
+ * chunk blockIdx.x + gridDim.x, ... with the grid sized so that all make the same number of trips; within a chunk the elements in front of
+ * the first 16-byte line of the buffers and behind the last whole one are handled one float at a time, the body as one float4 per thread.  That
+ * needs all buffers of a call to sit alike relative to 16 bytes (torch allocations do); otherwise the whole chunk goes one float at a time.  For the
+ * streaming order, sort the table by begin. */
+#define SEFD_OPTIM_CHUNK 1024
+#define SEFD_OPTIM_MAX_GROUPS 8
+#define SEFD_OPTIM_DECOUPLED 1u /* flags bit 0: AdamW's decay, p *= 1 - lr * weight_decay; otherwise L2: g += weight_decay * p */
+#define SEFD_OPTIM_AMSGRAD 2u   /* flags bit 1: max_exp_avg_sq = max(max_exp_avg_sq, exp_avg_sq) is kept and used in the denominator */
+typedef struct sefd_optim_chunk {
+  int64_t begin;
+  int32_t count; /* 1 .. SEFD_OPTIM_CHUNK */
+  int32_t group; /* 0 .. ngroups - 1 */
+} sefd_optim_chunk;
+typedef struct sefd_optim_group {
+  float lr, beta1, beta2, eps, weight_decay;
+  uint32_t flags;
+} sefd_optim_group;
+/* Global L2 norm of grad * grad_scale over the chunks of the table (table_host == table_dev == NULL: over all n elements) and the clip
+ * coefficient of torch.nn.utils.clip_grad_norm_: out[0] = norm, out[1] = min(1, max_norm / (norm + 1e-6)); both stay in device memory.  Squares
+ * and sums are fp64; two launches (per-workgroup partial sums, then one workgroup that adds them in index order), no atomics: the same data give
+ * the same bits.  A non-finite norm (a NaN or Inf element, sefd_plan_status_poison's among them) is written as it is and out[1] becomes NaN;
+ * norm 0 gives 1.  ws: sefd_grad_norm_ws_floats(n) floats on an 8-byte boundary.  -1, nothing launched: n < 1, max_norm < 0 or NaN, a NULL or
+ * misaligned pointer, one table pointer without the other, nchunks < 1 with a table, a chunk outside [0, n) or with count outside 1 .. SEFD_OPTIM_CHUNK. */
+int64_t sefd_grad_norm_ws_floats(int64_t n);
+int32_t sefd_grad_norm(const float* grad, int64_t n, float grad_scale, float max_norm, const sefd_optim_chunk* table_host,
+                       const sefd_optim_chunk* table_dev, int32_t nchunks, float* ws, float* out, void* stream);
+/* ONE launch for all groups.  Per element of a chunk, in torch's order:  g = grad * grad_scale * coef[0] (coef NULL: 1);  weight_decay != 0:
+ * decoupled p *= 1 - lr * weight_decay (as p - (lr * weight_decay) * p, one fma), else g += weight_decay * p;  m, v as in sefd_adam_step;  amsgrad: vmax = max(vmax, v) and the denominator
+ * takes vmax;  p -= lr / bc1 * m / (sqrt(v or vmax) / sqrt(bc2) + eps), the bias corrections formed on the host in double from `step` (1-based, one
+ * count for all groups).  grad is only read: clipping is the factor coef, typically out + 1 of sefd_grad_norm on the same stream.  The whole update
+ * is skipped, before anything is written, while *skip_if_set != 0, *skip_if_nan is NaN (both as in sefd_adam_step_guarded_dp) or coef[0] is NaN.
+ * max_exp_avg_sq may be NULL when no group has SEFD_OPTIM_AMSGRAD.  Traffic: 28 bytes per element, 36 with amsgrad.
+ * -1, nothing launched: n < 1, step < 1, ngroups outside 1 .. SEFD_OPTIM_MAX_GROUPS, a NULL buffer, groups or table pointer, nchunks < 1, an amsgrad
+ * group without max_exp_avg_sq, a chunk outside [0, n), with count outside 1 .. SEFD_OPTIM_CHUNK or with a group outside 0 .. ngroups - 1. */
+int32_t sefd_optim_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, int32_t step,
+                        const sefd_optim_group* groups, int32_t ngroups, const sefd_optim_chunk* table_host, const sefd_optim_chunk* table_dev,
+                        int32_t nchunks, float grad_scale, const float* coef, const int32_t* skip_if_set, const float* skip_if_nan, void* stream);
+
 /* ---- tuning table ------------------------------------------------------------------------------------
  * The planner's and the launchers' tuning knobs (tile thresholds, fusions, lane placement, ...: INTEGRATION.md section 6) live in ONE process-wide
  * table, not in the environment: a plan is a function of its sefd_model_config and of this table at the moment sefd_plan_create runs; launch- and
