@@ -14,8 +14,8 @@ import torch.nn as nn
 from . import config as cfg
 from . import _lib
 from .frontend_consts import stft_kernels
-from .plan import (ARENA_COUNT, ARENA_CONST, ARENA_GRAD, ARENA_IO, ARENA_PARAM, ARENA_STATE, ARENA_WS, PHASE_BWD,
-                   PHASE_FWD, RUN_WAVE_ONLY, Plan)
+from .plan import PHASE_BWD, PHASE_FWD, RUN_WAVE_ONLY, Plan
+from .runtime import Runtime, cached
 from . import tools_for_loss as tfl
 
 
@@ -26,15 +26,10 @@ def _default_fft_len(win_len):
 
 
 def _frontend_runtime(mod, model, B, n, device, complex_io):
-    """(plan, arenas) of a ConvSTFT / ConviSTFT module at batch B and n = clip length L / frame count T, cached on the module."""
-    key = (model, B, n, str(device), complex_io)
-    rt = mod._runtimes.get(key)
-    if rt is None:
-        plan = Plan(B, n, win_len=mod.win_len, win_inc=mod.stride, fft_len=mod.dim, model=model, win_type=mod.win_type,
-                    feature_type="complex" if complex_io else "real")
-        rt = (plan, plan.alloc_arenas(device))
-        mod._runtimes[key] = rt
-    return rt
+    """Runtime of a ConvSTFT / ConviSTFT module at batch B and n = clip length L / frame count T, cached on the module."""
+    return cached(mod._runtimes, (model, B, n, str(device), complex_io), lambda: Runtime.owned(
+        Plan(B, n, win_len=mod.win_len, win_inc=mod.stride, fft_len=mod.dim, model=model, win_type=mod.win_type,
+             feature_type="complex" if complex_io else "real"), device))
 
 
 def _check_frontend_input(name, *tensors):
@@ -45,35 +40,66 @@ def _check_frontend_input(name, *tensors):
             raise RuntimeError(f"sefd {name} is built for float32 only, got {t.dtype}")
 
 
-class _FrontendFunction(torch.autograd.Function):
-    """One ConvSTFT / ConviSTFT plan (csrc/plan_frontend.cpp) at its IO boundary: `ins` / `outs` / `gouts` / `gins` are lists of
-    (IO buffer name, shape).  `keep` names the plan buffers the backward phase reads besides the cotangents (the spectrum under (mags, phase),
-    the polar inputs): they are cloned when an input requires grad and put back before the backward phase, so any number of forwards of one
-    shape may precede their backwards.  The backward phase runs only when autograd asks for it; double backward is not supported."""
+_STALE = "sefd: a later forward of the same shape overwrote the activations this backward needs"
+
+
+def _next_dropout_seed(rt):
+    rt.view("io.seed").view(torch.int32)[:1].add_(1)        # fresh dropout masks every forward (device-side counter)
+
+
+class _PlanFunction(torch.autograd.Function):
+    """One plan with a forward and a backward phase at its IO boundary, described by views into the runtime's arenas: `ins` (where the input tensors go),
+    `outs` (what is returned, as float32 copies), `gouts` (where the cotangents go; a missing one zero-fills its view), `gins` (the input gradients, one per
+    leading input; inputs beyond them get none) and `zero` (views cleared before every backward).  The tensors after the inputs are the owner's parameters:
+    each gets its slice of one clone of the flat gradient arena.
+    The activations the backward phase reads live in the runtime's arenas.  keep None: a later forward of the same shape invalidates this one's backward
+    (stamp; `stale` is the message).  keep = views (the parameter-free frontends: the spectrum under (mags, phase), the polar inputs): they are cloned when
+    an input requires grad and put back before the backward phase, so any number of forwards of one shape may precede their backwards.
+    The backward phase runs only when autograd asks for it; double backward is not supported."""
 
     @staticmethod
-    def forward(ctx, rt, ins, outs, gouts, gins, keep, *tensors):
-        plan, ar = rt
-        for (name, shape), t in zip(ins, tensors):
-            plan.io(ar, name, shape).copy_(t.reshape(shape))
-        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
-        ctx.rt, ctx.gouts, ctx.gins, ctx.keep = rt, gouts, gins, keep
-        ctx.in_shapes = [t.shape for t in tensors]
-        if any(ctx.needs_input_grad):
-            ctx.save_for_backward(*[plan.view(ar, name).clone() for name in keep])
-        res = tuple(plan.io(ar, name, shape).clone() for name, shape in outs)
+    def forward(ctx, rt, owner, b, *tensors):
+        for dst, t in zip(b["ins"], tensors):
+            dst.copy_(t.reshape(dst.shape))
+        if b["seed"]:
+            _next_dropout_seed(rt)
+        rt.run(PHASE_FWD)
+        rt.stamp += 1                                # the saved activations live in the runtime's arena, not in ctx
+        ctx.rt, ctx.owner, ctx.b, ctx.stamp = rt, owner, b, rt.stamp
+        ctx.in_shapes = [t.shape for t in tensors[:len(b["gins"])]]
+        if b["keep"] is not None and any(ctx.needs_input_grad):
+            ctx.save_for_backward(*[v.clone() for v in b["keep"]])
+        res = tuple(v.to(torch.float32, copy=True) for v in b["outs"])      # activation dtype -> fp32 at the boundary
         return res if len(res) > 1 else res[0]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, *grads):
-        plan, ar = ctx.rt
-        for name, t in zip(ctx.keep, ctx.saved_tensors):
-            plan.view(ar, name).copy_(t)
-        for (name, shape), g in zip(ctx.gouts, grads):
-            plan.io(ar, name, shape).copy_(g.reshape(shape))
-        plan.run(PHASE_BWD, ar, torch.cuda.current_stream().cuda_stream)
-        return (None,) * 6 + tuple(plan.io(ar, name, shape).clone().reshape(ish) for (name, shape), ish in zip(ctx.gins, ctx.in_shapes))
+        rt, owner, b = ctx.rt, ctx.owner, ctx.b
+        if b["keep"] is not None:
+            for v, t in zip(b["keep"], ctx.saved_tensors):
+                v.copy_(t)
+        elif ctx.stamp != rt.stamp:
+            raise RuntimeError(b["stale"])
+        for v in b["zero"]:
+            v.zero_()
+        for dst, g in zip(b["gouts"], grads):
+            if g is None:
+                dst.zero_()
+            else:
+                dst.copy_(g.reshape(dst.shape))
+        rt.run(PHASE_BWD)
+        pgrads = ()
+        if owner is not None:
+            flat = owner._flat_grad.clone()
+            pgrads = tuple(flat[off:off + n].view(shape) for (off, n, shape) in owner._param_slices)
+        gins = tuple(v.clone().reshape(ish) for v, ish in zip(b["gins"], ctx.in_shapes))
+        return (None,) * 3 + gins + (None,) * (len(b["ins"]) - len(gins)) + pgrads
+
+
+def _plan_apply(rt, owner, tensors, ins, outs, gouts, gins=(), zero=(), keep=None, seed=False, stale=_STALE):
+    params = [p for _, p in owner._trainable()] if owner is not None else []
+    return _PlanFunction.apply(rt, owner, dict(ins=ins, outs=outs, gouts=gouts, gins=gins, zero=zero, keep=keep, seed=seed, stale=stale), *tensors, *params)
 
 
 class ConvSTFT(nn.Module):
@@ -96,14 +122,13 @@ class ConvSTFT(nn.Module):
             raise ValueError(f"ConvSTFT takes [B, L] or [B, 1, L], got {tuple(inputs.shape)}")
         B, L = inputs.shape[0], inputs.shape[-1]
         rt = _frontend_runtime(self, "ConvSTFT", B, L, inputs.device, self.feature_type == 'complex')
-        NF, T = rt[0].NF, rt[0].T
+        NF, T = rt.plan.NF, rt.plan.T
         if self.feature_type == 'complex':
-            outs, gouts = [("out", (B, 2 * NF, T))], [("grad_out", (B, 2 * NF, T))]
+            outs, gouts, keep = [rt.io("out", (B, 2 * NF, T))], [rt.io("grad_out", (B, 2 * NF, T))], []
         else:
-            outs = [("mags", (B, NF, T)), ("phase", (B, NF, T))]
-            gouts = [("grad_mags", (B, NF, T)), ("grad_phase", (B, NF, T))]
-        keep = [] if self.feature_type == 'complex' else ["spec"]
-        return _FrontendFunction.apply(rt, [("wav", (B, L))], outs, gouts, [("grad_wav", (B, L))], keep, inputs)
+            outs = [rt.io("mags", (B, NF, T)), rt.io("phase", (B, NF, T))]
+            gouts, keep = [rt.io("grad_mags", (B, NF, T)), rt.io("grad_phase", (B, NF, T))], [rt.view("spec")]
+        return _plan_apply(rt, None, (inputs,), [rt.io("wav", (B, L))], outs, gouts, [rt.io("grad_wav", (B, L))], keep=keep)
 
 
 class ConviSTFT(nn.Module):
@@ -134,75 +159,15 @@ class ConviSTFT(nn.Module):
         rt = _frontend_runtime(self, "ConviSTFT", B, T, inputs.device, phase is None)
         Lout = (T - 1) * self.stride + self.win_len - 2 * (self.win_len - self.stride)
         if phase is None:
-            ins, gins, args, keep = [("in", (B, 2 * NF, T))], [("grad_in", (B, 2 * NF, T))], (inputs,), []
+            ins, gins, args, keep = [rt.io("in", (B, 2 * NF, T))], [rt.io("grad_in", (B, 2 * NF, T))], (inputs,), []
         else:
-            ins = [("mags", (B, NF, T)), ("phase", (B, NF, T))]
-            gins, args, keep = [("grad_mags", (B, NF, T)), ("grad_phase", (B, NF, T))], (inputs, phase), ["io.mags", "io.phase"]
-        wav = _FrontendFunction.apply(rt, ins, [("wav", (B, Lout))], [("grad_wav", (B, Lout))], gins, keep, *args)
+            ins = [rt.io("mags", (B, NF, T)), rt.io("phase", (B, NF, T))]
+            gins, args, keep = [rt.io("grad_mags", (B, NF, T)), rt.io("grad_phase", (B, NF, T))], (inputs, phase), ins
+        wav = _plan_apply(rt, None, args, ins, [rt.io("wav", (B, Lout))], [rt.io("grad_wav", (B, Lout))], gins, keep=keep)
         return wav.unsqueeze(1)
 
 
 # (ComplexConv2d, ComplexConvTranspose2d, ComplexBatchNorm, NavieComplexLSTM: below, on _SefdModule)
-
-
-# ------------------------------------------------------------------------------------------ device runtime
-class _Runtime:
-    """Plan + device arenas for one (B, L, training, device) combination."""
-
-    def __init__(self, owner, B, L, training, device):
-        self.plan = owner._make_plan(B, L, training)
-        p = self.plan
-        self.arenas = [None] * ARENA_COUNT
-        self.arenas[ARENA_WS] = torch.zeros(max(p.arena_bytes[ARENA_WS], 256), dtype=torch.uint8, device=device)
-        self.arenas[ARENA_CONST] = torch.from_numpy(p.const_image()).to(device)
-        self.arenas[ARENA_IO] = torch.zeros(p.arena_bytes[ARENA_IO], dtype=torch.uint8, device=device)
-        self.arenas[ARENA_PARAM] = owner._flat_param
-        self.arenas[ARENA_GRAD] = owner._flat_grad
-        self.arenas[ARENA_STATE] = owner._flat_state
-        T, NF = p.T, p.NF
-        self.wav = p.io(self.arenas, "wav", (B, L))
-        self.out_wav = p.io(self.arenas, "out_wav", (B, L))
-        # ConviSTFT returns the samples the frames cover (tools_for_model.py:111): fewer than L when the hop does not tile the padded clip
-        self.Lout = min(L, (T - 1) * p.cfg.hop + p.cfg.win_len - 2 * (p.cfg.win_len - p.cfg.hop))
-        self.out_real = p.io(self.arenas, "out_real", (B, NF, T))
-        self.out_imag = p.io(self.arenas, "out_imag", (B, NF, T))
-        self.g_wav = p.io(self.arenas, "grad_wav", (B, L))
-        self.g_real = p.io(self.arenas, "grad_real", (B, NF, T))
-        self.g_imag = p.io(self.arenas, "grad_imag", (B, NF, T))
-        self.tgt = p.io(self.arenas, "tgt", (B, L)) if "io.tgt" in p.buffer_names() else None
-
-    def run(self, phase):
-        self.plan.run(phase, self.arenas, torch.cuda.current_stream().cuda_stream)
-
-
-class _DCCRNFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, owner, rt, inputs, targets, *params):
-        rt.wav.copy_(inputs)
-        if rt.tgt is not None:
-            rt.tgt.copy_(targets)
-        rt.run(PHASE_FWD)
-        rt.stamp = getattr(rt, "stamp", 0) + 1     # the saved activations live in the runtime's arena, not in ctx
-        ctx.owner, ctx.rt, ctx.stamp = owner, rt, rt.stamp
-        ctx.n = len(params)
-        return rt.out_real.clone(), rt.out_imag.clone(), rt.out_wav[:, :rt.Lout].clone()
-
-    @staticmethod
-    def backward(ctx, g_real, g_imag, g_wav):
-        rt, owner = ctx.rt, ctx.owner
-        if ctx.stamp != rt.stamp:
-            raise RuntimeError("sefd: a later forward of the same (batch, length, mode) overwrote the activations this backward needs; "
-                               "call backward before the next forward of that shape")
-        rt.g_wav[:, rt.Lout:].zero_()                # samples behind the last frame are not part of the output
-        for dst, g in ((rt.g_real, g_real), (rt.g_imag, g_imag), (rt.g_wav[:, :rt.Lout], g_wav)):
-            if g is None:
-                dst.zero_()
-            else:
-                dst.copy_(g)
-        rt.run(PHASE_BWD)
-        flat = owner._flat_grad.clone()
-        grads = [flat[off:off + n].view(shape) for (off, n, shape) in owner._param_slices]
-        return (None, None, None, None) + tuple(grads)
 
 
 # ------------------------------------------------------------------------------------------ shared machinery
@@ -210,7 +175,6 @@ class _SefdModule(nn.Module):
     """Flat parameter storage + per-(B, L) device runtimes shared by the HIP-backed models."""
 
     def _init_runtime_state(self):
-        import weakref
         self._flat_param = self._flat_grad = self._flat_state = self._flat_nbt = None
         self._param_slices = None
         self._runtimes = {}
@@ -275,16 +239,32 @@ class _SefdModule(nn.Module):
         if not self._flat_ok(device):
             self._flatten(device)
         key = (B, L, bool(self.training), self.masking_mode, self.act_dtype, getattr(self, "_bn_world", 1), getattr(self, "_grad_buckets", 1))
-        rt = self._runtimes.get(key)
-        if rt is None:
-            rt = _Runtime(self, B, L, bool(self.training), device)
-            rt.plan.owner = weakref.ref(self)            # running it makes it this model's `_status_plan` (guarded Adam, checkpoint check)
-            # the plan's parameter table must agree with the module tree (names, order, sizes)
-            names = [n for n, _ in self._trainable()]
-            assert names == list(rt.plan.params.keys()), "parameter order differs from the plan"
-            assert [s[0] for s in self._param_slices] == [v[0] for v in rt.plan.params.values()]
-            self._runtimes[key] = rt
-        return rt
+
+        def make():
+            rt = Runtime.bound(self._make_plan(B, L, bool(self.training)), self, device)
+            p = rt.plan
+            T, NF = p.T, p.NF
+            rt.wav = rt.io("wav", (B, L))
+            rt.out_wav = rt.io("out_wav", (B, L))
+            # ConviSTFT returns the samples the frames cover (tools_for_model.py:111): fewer than L when the hop does not tile the padded clip
+            rt.Lout = min(L, (T - 1) * p.cfg.hop + p.cfg.win_len - 2 * (p.cfg.win_len - p.cfg.hop))
+            rt.out_real = rt.io("out_real", (B, NF, T))
+            rt.out_imag = rt.io("out_imag", (B, NF, T))
+            rt.g_wav = rt.io("grad_wav", (B, L))
+            rt.g_real = rt.io("grad_real", (B, NF, T))
+            rt.g_imag = rt.io("grad_imag", (B, NF, T))
+            rt.tgt = rt.io("tgt", (B, L)) if "io.tgt" in p.buffer_names() else None
+            return rt
+        return cached(self._runtimes, key, make)
+
+    def _forward_plan(self, rt, inputs, targets=None):
+        """The model's plan under autograd: (out_real, out_imag, out_wav cropped to the samples the frames cover); gradients to the parameters."""
+        tgt = rt.tgt is not None
+        return _plan_apply(rt, self, (inputs, targets) if tgt else (inputs,), [rt.wav, rt.tgt] if tgt else [rt.wav],
+                           [rt.out_real, rt.out_imag, rt.out_wav[:, :rt.Lout]], [rt.g_real, rt.g_imag, rt.g_wav[:, :rt.Lout]],
+                           zero=[rt.g_wav[:, rt.Lout:]],                 # samples behind the last frame are not part of the output
+                           stale="sefd: a later forward of the same (batch, length, mode) overwrote the activations this backward needs; "
+                                 "call backward before the next forward of that shape")
 
     def get_params(self, weight_decay=0.0):
         weights, biases = [], []
@@ -411,20 +391,29 @@ class _SefdModule(nn.Module):
             rt.plan.run_cb(PHASE_BWD, rt.arenas, stream, -1, None, flags=wave_only)
         else:
             rt.run(PHASE_BWD)
-        if exchange is not None and exchange.active:         # DDP: sum gradients over ranks (RCCL), average inside Adam
-            # a rank whose plan gave up poisons an element of the LAST bucket: every rank's Adam then skips this step (optim.step_flat)
-            optimizer.nan_guard = self._dp_guard = self._flat_grad[0:1]
-            rt.plan.status_poison(optimizer.nan_guard, stream)
-            if bucket is not None:
-                exchange.begin(self._flat_grad[:bucket[1]])
-                exchange.finish(self._flat_grad)
-            else:
-                exchange.all_reduce(self._flat_grad)
-            optimizer.grad_scale = exchange.grad_scale
-        optimizer.step_flat()
-        if exchange is not None and exchange.active:
-            _dp_guard_tick(self)
+        _finish_step(self, rt.plan, optimizer, exchange, stream, self._flat_grad[0:1], None if bucket is None else [self._flat_grad[:bucket[1]]])
         return loss
+
+
+def _finish_step(model, plan, optimizer, exchange, stream, guard, rest):
+    """What a train_step does after the backward phase: all-reduce, Adam, guard.  `guard`: the one-element slice of the flat gradient, in the LAST bucket,
+    that tells every rank of a faulty one.  `rest`: the slices still to be all-reduced after the bucket that was started under the backward (None: no
+    bucket was started; the whole gradient goes in one all-reduce)."""
+    active = exchange is not None and exchange.active
+    if active:                                               # DDP: sum gradients over ranks (RCCL), average inside Adam
+        # a rank whose plan gave up poisons an element of the LAST bucket: every rank's Adam then skips this step (optim.step_flat)
+        optimizer.nan_guard = model._dp_guard = guard
+        plan.status_poison(guard, stream)
+        if rest is not None:
+            for g in rest:
+                exchange.begin(g)
+            exchange.finish(model._flat_grad)
+        else:
+            exchange.all_reduce(model._flat_grad)
+        optimizer.grad_scale = exchange.grad_scale
+    optimizer.step_flat()
+    if active:
+        _dp_guard_tick(model)
 
 
 DP_GUARD_EVERY = 16          # data parallel: the all-reduced guard element is looked at on the host every this many steps (one 4-byte read behind a sync)
@@ -450,30 +439,12 @@ def _dp_guard_tick(model):
 
 
 # ------------------------------------------------------------------------------------------ the layers of tools_for_model.py:126-607
-class _LayerFunction(torch.autograd.Function):
-    """One ConvLayer / ComplexBatchNorm plan (csrc/plan_layers.cpp) at its reference-layout boundary: io.x -> io.y, io.grad_y -> io.grad_x and the flat
-    gradient arena.  The saved activations live in the runtime's workspace: a later forward of the same shape invalidates this one's backward (stamp)."""
-
-    @staticmethod
-    def forward(ctx, owner, rt, x, out_shape, *params):
-        plan, ar = rt
-        plan.io(ar, "x", tuple(x.shape)).copy_(x)
-        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
-        plan.stamp = getattr(plan, "stamp", 0) + 1
-        ctx.owner, ctx.rt, ctx.in_shape, ctx.out_shape, ctx.stamp = owner, rt, tuple(x.shape), out_shape, plan.stamp
-        return plan.io(ar, "y", out_shape).clone()
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        plan, ar = ctx.rt
-        if ctx.stamp != plan.stamp:
-            raise RuntimeError("sefd: a later forward of the same shape overwrote the activations this backward needs")
-        plan.io(ar, "grad_y", ctx.out_shape).copy_(g)
-        plan.run(PHASE_BWD, ar, torch.cuda.current_stream().cuda_stream)
-        flat = ctx.owner._flat_grad.clone()
-        return (None, None, plan.io(ar, "grad_x", ctx.in_shape).clone(), None) + tuple(
-            flat[off:off + n].view(shape) for (off, n, shape) in ctx.owner._param_slices)
+def _xy_apply(rt, owner, x, out_shape, y=None, seed=False):
+    """The boundary of a ConvLayer / ComplexBatchNorm / ComplexLSTM / SequenceModel plan: io.x -> io.y (or the view `y`), io.grad_y -> io.grad_x and the
+    flat gradient arena."""
+    shape = tuple(x.shape)
+    return _plan_apply(rt, owner, (x,), [rt.io("x", shape)], [rt.io("y", out_shape) if y is None else y], [rt.io("grad_y", out_shape)],
+                       [rt.io("grad_x", shape)], seed=seed)
 
 
 def _pair(v):
@@ -517,14 +488,9 @@ class _ConvLayer(_SefdModule):
     def _layer_runtime(self, B, F, T, device):
         if not self._flat_ok(device):
             self._flatten(device)
-        key = ("conv", B, F, T, self.act_dtype, str(device))
-        rt = self._runtimes.get(key)
-        if rt is None:
-            plan = Plan(B, T, act_dtype=self.act_dtype, training=True, model="ConvLayer",
-                        conv=dict(self._geo, causal=bool(getattr(self, "causal", True)), F=F))
-            rt = _layer_arenas(self, plan, device)
-            self._runtimes[key] = rt
-        return rt
+        return cached(self._runtimes, ("conv", B, F, T, self.act_dtype, str(device)), lambda: Runtime.bound(
+            Plan(B, T, act_dtype=self.act_dtype, training=True, model="ConvLayer",
+                 conv=dict(self._geo, causal=bool(getattr(self, "causal", True)), F=F)), self, device))
 
     def forward(self, inputs):
         name, g = self._KIND, self._geo
@@ -534,26 +500,13 @@ class _ConvLayer(_SefdModule):
         if inputs.dim() != 4 or inputs.shape[1] != g["in_channels"]:
             raise ValueError(f"{name} takes [B, {g['in_channels']}, F, T], got {tuple(inputs.shape)}")
         B, _, F, T = inputs.shape
-        plan, ar = rt = self._layer_runtime(B, F, T, inputs.device)
+        rt = self._layer_runtime(B, F, T, inputs.device)
         k, p = g["kernel_size"], g["padding"]
         if "Transpose" in name:
             Fo = (F - 1) * g["stride_f"] - 2 * p[0] + k[0] + g["output_padding_f"]
         else:
             Fo = (F + 2 * p[0] - k[0]) // g["stride_f"] + 1
-        return _LayerFunction.apply(self, rt, inputs.contiguous(), (B, g["out_channels"], Fo, plan.T), *[q for _, q in self._trainable()])
-
-
-def _layer_arenas(owner, plan, device):
-    """(plan, arenas) of a layer that owns its flat parameters; the plan's parameter table must agree with the module (names, order, offsets)."""
-    plan.owner = weakref.ref(owner)
-    assert [n for n, _ in owner._trainable()] == list(plan.params.keys()), "parameter order differs from the plan"
-    assert [s[0] for s in owner._param_slices] == [v[0] for v in plan.params.values()]
-    ar = [None] * ARENA_COUNT
-    ar[ARENA_WS] = torch.zeros(max(plan.arena_bytes[ARENA_WS], 256), dtype=torch.uint8, device=device)
-    ar[ARENA_CONST] = torch.from_numpy(plan.const_image()).to(device)
-    ar[ARENA_IO] = torch.zeros(plan.arena_bytes[ARENA_IO], dtype=torch.uint8, device=device)
-    ar[ARENA_PARAM], ar[ARENA_GRAD], ar[ARENA_STATE] = owner._flat_param, owner._flat_grad, owner._flat_state
-    return plan, ar
+        return _xy_apply(rt, self, inputs.contiguous(), (B, g["out_channels"], Fo, rt.plan.T))
 
 
 def _init_conv(*convs):
@@ -685,57 +638,25 @@ class ComplexBatchNorm(_SefdModule):
         return (f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, affine={self.affine}, "
                 f"track_running_stats={self.track_running_stats}")
 
+    def _cbn_runtime(self, B, S, device):
+        if not self._flat_ok(device):
+            self._flatten(device)
+        key = ("cbn", B, S, bool(self.training), float(self.eps), float(self.momentum), self.act_dtype, str(device))
+        return cached(self._runtimes, key, lambda: Runtime.bound(
+            Plan(B, S, act_dtype=self.act_dtype, training=bool(self.training), model="ComplexBatchNorm",
+                 cbn=dict(num_features=2 * self.num_features, eps=self.eps, momentum=self.momentum)), self, device))
+
     def forward(self, inputs):
         _check_frontend_input("ComplexBatchNorm", inputs)
         C2 = 2 * self.num_features
         if inputs.dim() < 3 or inputs.shape[1] != C2:
             raise ValueError(f"ComplexBatchNorm takes [B, {C2}, *rest] with at least one trailing dimension, got {tuple(inputs.shape)}")
         B, S = inputs.shape[0], int(inputs[0, 0].numel())
-        device = inputs.device
-        if not self._flat_ok(device):
-            self._flatten(device)
-        key = ("cbn", B, S, bool(self.training), float(self.eps), float(self.momentum), self.act_dtype, str(device))
-        rt = self._runtimes.get(key)
-        if rt is None:
-            plan = Plan(B, S, act_dtype=self.act_dtype, training=bool(self.training), model="ComplexBatchNorm",
-                        cbn=dict(num_features=C2, eps=self.eps, momentum=self.momentum))
-            rt = _layer_arenas(self, plan, device)
-            self._runtimes[key] = rt
+        rt = self._cbn_runtime(B, S, inputs.device)
         if self.training:
             self._flat_nbt += 1
-        y = _LayerFunction.apply(self, rt, inputs.contiguous().view(B, C2, S), (B, C2, S), *[q for _, q in self._trainable()])
+        y = _xy_apply(rt, self, inputs.contiguous().view(B, C2, S), (B, C2, S))
         return y.view(inputs.shape)
-
-
-class _CLSTMFunction(torch.autograd.Function):
-    """One ComplexLSTM plan (csrc/plan_clstm.cpp) at its batch-major boundary: x [B, T, 2 IP] (real | imaginary) -> y [B, T, 2 P], or without a
-    projection the directions' combined outputs [D, B, T, 2 H].  The saved activations live in the runtime's workspace (stamp, as _LayerFunction)."""
-
-    @staticmethod
-    def forward(ctx, owner, rt, x, *params):
-        plan, ar = rt
-        plan.io(ar, "x", tuple(x.shape)).copy_(x)
-        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
-        plan.stamp = getattr(plan, "stamp", 0) + 1
-        B, T = x.shape[0], x.shape[1]
-        D, H, P = (2 if owner.bidirectional else 1), owner.rnn_units, owner.projection_dim
-        ctx.owner, ctx.rt, ctx.in_shape, ctx.stamp = owner, rt, tuple(x.shape), plan.stamp
-        ctx.out_shape = (B, T, 2 * P) if P is not None else (D, B, T, 2 * H)
-        if P is not None:
-            return plan.io(ar, "y", ctx.out_shape).clone()
-        return plan.view(ar, "hc").view(ctx.out_shape).to(torch.float32, copy=True)      # activation dtype -> fp32 at the boundary
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        plan, ar = ctx.rt
-        if ctx.stamp != plan.stamp:
-            raise RuntimeError("sefd: a later forward of the same shape overwrote the activations this backward needs")
-        plan.io(ar, "grad_y", ctx.out_shape).copy_(g)
-        plan.run(PHASE_BWD, ar, torch.cuda.current_stream().cuda_stream)
-        flat = ctx.owner._flat_grad.clone()
-        return (None, None, plan.io(ar, "grad_x", ctx.in_shape).clone()) + tuple(
-            flat[off:off + n].view(shape) for (off, n, shape) in ctx.owner._param_slices)
 
 
 class NavieComplexLSTM(_SefdModule):
@@ -770,15 +691,10 @@ class NavieComplexLSTM(_SefdModule):
     def _clstm_runtime(self, B, T, device):
         if not self._flat_ok(device):
             self._flatten(device)
-        key = ("clstm", B, T, self.act_dtype, str(device))
-        rt = self._runtimes.get(key)
-        if rt is None:
-            # one training-capable plan for both modes: the layer has no mode-dependent arithmetic, and inside a larger network the input gradient is
-            # needed in eval mode too
-            plan = Plan(B, T, act_dtype=self.act_dtype, training=True, model="ComplexLSTM", clstm=self._sizes)
-            rt = _layer_arenas(self, plan, device)
-            self._runtimes[key] = rt
-        return rt
+        # one training-capable plan for both modes: the layer has no mode-dependent arithmetic, and inside a larger network the input gradient is
+        # needed in eval mode too
+        return cached(self._runtimes, ("clstm", B, T, self.act_dtype, str(device)), lambda: Runtime.bound(
+            Plan(B, T, act_dtype=self.act_dtype, training=True, model="ComplexLSTM", clstm=self._sizes), self, device))
 
     def forward(self, inputs):
         if not isinstance(inputs, (list, tuple)) or len(inputs) != 2:
@@ -797,10 +713,13 @@ class NavieComplexLSTM(_SefdModule):
         if pad:
             real, imag = nn.functional.pad(real, (0, pad)), nn.functional.pad(imag, (0, pad))
         x = torch.cat([real, imag], 2).permute(1, 0, 2).contiguous()
-        out = _CLSTMFunction.apply(self, rt, x, *[q for _, q in self._trainable()])
-        if P is not None:
+        if P is not None:                            # batch-major boundary: x [B, T, 2 IP] (real | imaginary) -> y [B, T, 2 P]
+            out = _xy_apply(rt, self, x, (B, T, 2 * P))
             halves = (out[..., :P], out[..., P:])
-        else:                                        # [D, B, T, real | imag] -> forward | reverse on the last axis
+        else:                                        # the directions' combined outputs `hc`, in the activation dtype
+            D = 2 if self.bidirectional else 1
+            out = _xy_apply(rt, self, x, (D, B, T, 2 * H), y=rt.view("hc").view(D, B, T, 2 * H))
+            # [D, B, T, real | imag] -> forward | reverse on the last axis
             halves = tuple(torch.cat([out[d][..., p * H:(p + 1) * H] for d in range(out.shape[0])], -1) for p in (0, 1))
         return [h.permute(1, 0, 2).contiguous() for h in halves]
 
@@ -896,8 +815,7 @@ class DCCRN(_SefdModule):
         rt = self._runtime(B, L, inputs.device)
         if self.training:
             self._flat_nbt += 1
-        params = [p for _, p in self._trainable()]
-        out_real, out_imag, out_wav = _DCCRNFunction.apply(self, rt, inputs, None, *params)
+        out_real, out_imag, out_wav = self._forward_plan(rt, inputs)
         if self.masking_mode == 'Direct(None make)':            # spectral mapping (models.py:232-250): spectra of the target too
             target_real, target_imag = self._stft_ref(targets)
             return out_real, target_real, out_imag, target_imag, out_wav
@@ -918,18 +836,14 @@ class DCCRN(_SefdModule):
         """ConvSTFT 'complex' of a waveform batch in the reference layout: ([B,257,T] real, [B,257,T] imag), no grad."""
         wav = wav.detach().float().contiguous()
         B, L = wav.shape
-        key = ("stft", B, L, str(wav.device), str(self.win_type))
-        fe = self._runtimes.get(key)
-        if fe is None:
-            # the reference forms target / clean spectra with self.stft, i.e. the MODEL's window (models.py:237, 306-308): round 5 built this plan
-            # with the default Hann window whatever win_type was - silently wrong losses for 'hamming' / None (ADVICE r5, goldens dccrn_hamming_direct_mse, _lms)
-            plan = Plan(B, L, win_len=self.win_len, win_inc=self.win_inc, fft_len=self.fft_len, model="STFT", win_type=self.win_type)
-            fe = (plan, plan.alloc_arenas(wav.device))
-            self._runtimes[key] = fe
-        plan, ar = fe
-        plan.io(ar, "wav", (B, L)).copy_(wav)
-        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
-        return plan.io(ar, "out_real", (B, plan.NF, plan.T)).clone(), plan.io(ar, "out_imag", (B, plan.NF, plan.T)).clone()
+        # the reference forms target / clean spectra with self.stft, i.e. the MODEL's window (models.py:237, 306-308): round 5 built this plan
+        # with the default Hann window whatever win_type was - silently wrong losses for 'hamming' / None (ADVICE r5, goldens dccrn_hamming_direct_mse, _lms)
+        fe = cached(self._runtimes, ("stft", B, L, str(wav.device), str(self.win_type)), lambda: Runtime.owned(
+            Plan(B, L, win_len=self.win_len, win_inc=self.win_inc, fft_len=self.fft_len, model="STFT", win_type=self.win_type), wav.device))
+        fe.io("wav", (B, L)).copy_(wav)
+        fe.run(PHASE_FWD)
+        NF, T = fe.plan.NF, fe.plan.T
+        return fe.io("out_real", (B, NF, T)).clone(), fe.io("out_imag", (B, NF, T)).clone()
 
 
 class CRN(_SefdModule):
@@ -996,8 +910,7 @@ class CRN(_SefdModule):
         rt = self._runtime(B, L, inputs.device)
         if self.training:
             self._flat_nbt += 1
-        params = [p for _, p in self._trainable()]
-        est_mags, target_mags, out_wav = _DCCRNFunction.apply(self, rt, inputs, targets.float().contiguous(), *params)
+        est_mags, target_mags, out_wav = self._forward_plan(rt, inputs, targets.float().contiguous())
         return est_mags, target_mags.detach(), out_wav
 
     def loss(self, estimated, target, out_mags=0, target_mags=0, perceptual=False):
@@ -1007,32 +920,6 @@ class CRN(_SefdModule):
 
 
 # ------------------------------------------------------------------------------------------ FullSubNet (models.py:568-682)
-class _SeqFunction(torch.autograd.Function):
-    """One SequenceModel plan (csrc/plan_seq.cpp) at its time-major boundary: x [T, B, IP] -> pre-activation y [T, B, O]."""
-
-    @staticmethod
-    def forward(ctx, owner, rt, xt, *params):
-        plan, ar = rt
-        T, B, IP = xt.shape
-        plan.io(ar, "x", (T, B, IP)).copy_(xt)
-        plan.view(ar, "io.seed").view(torch.int32)[:1].add_(1)        # fresh dropout masks every forward (device-side counter)
-        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
-        plan.stamp = getattr(plan, "stamp", 0) + 1
-        ctx.owner, ctx.rt, ctx.shape, ctx.stamp = owner, rt, (T, B, IP), plan.stamp
-        return plan.io(ar, "y", (T, B, plan.NF_out)).clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        plan, ar = ctx.rt
-        if ctx.stamp != plan.stamp:
-            raise RuntimeError("sefd: a later forward of the same shape overwrote the activations this backward needs")
-        T, B, IP = ctx.shape
-        plan.io(ar, "grad_y", (T, B, plan.NF_out)).copy_(g)
-        plan.run(PHASE_BWD, ar, torch.cuda.current_stream().cuda_stream)
-        flat = ctx.owner._flat_grad.clone()
-        return (None, None, plan.io(ar, "grad_x", (T, B, IP)).clone()) + tuple(flat[off:off + n].view(shape) for (off, n, shape) in ctx.owner._param_slices)
-
-
 class SequenceModel(_SefdModule):
     """Same constructor and state_dict as the reference (tools_for_model.py:726-795): nn.LSTM or nn.GRU of any depth, optionally bidirectional
     (dropout=0.8 between the layers), + Linear (+ activation).  As a child of FullSubNet it is a parameter holder: FullSubNet owns the flat arenas
@@ -1061,23 +948,9 @@ class SequenceModel(_SefdModule):
         if not self._flat_ok(device):
             self._flatten(device)
         keep = self.dropout_keep if self.training else 1.0
-        key = ("seq", B, T, bool(self.training), keep, self.act_dtype)
-        rt = self._runtimes.get(key)
-        if rt is None:
-            # a training-capable plan in eval mode too (keep = 1): inside a larger network the input gradient is needed in either mode
-            plan = Plan(B, T, act_dtype=self.act_dtype, training=True, model="SequenceModel", seq=dict(self._seq, keep=keep))
-            plan.owner = weakref.ref(self)
-            plan.NF_out = self._seq["output_size"]
-            assert [n for n, _ in self._trainable()] == list(plan.params.keys()), "parameter order differs from the plan"
-            assert [s[0] for s in self._param_slices] == [v[0] for v in plan.params.values()]
-            ar = [None] * ARENA_COUNT
-            ar[ARENA_WS] = torch.zeros(max(plan.arena_bytes[ARENA_WS], 256), dtype=torch.uint8, device=device)
-            ar[ARENA_CONST] = torch.from_numpy(plan.const_image()).to(device)
-            ar[ARENA_IO] = torch.zeros(plan.arena_bytes[ARENA_IO], dtype=torch.uint8, device=device)
-            ar[ARENA_PARAM], ar[ARENA_GRAD], ar[ARENA_STATE] = self._flat_param, self._flat_grad, self._flat_state
-            rt = (plan, ar)
-            self._runtimes[key] = rt
-        return rt
+        # a training-capable plan in eval mode too (keep = 1): inside a larger network the input gradient is needed in either mode
+        return cached(self._runtimes, ("seq", B, T, bool(self.training), keep, self.act_dtype), lambda: Runtime.bound(
+            Plan(B, T, act_dtype=self.act_dtype, training=True, model="SequenceModel", seq=dict(self._seq, keep=keep)), self, device))
 
     def forward(self, x):
         """tools_for_model.py:779-795: x [B, F, T] -> [B, O, T]."""
@@ -1092,7 +965,7 @@ class SequenceModel(_SefdModule):
         xt = x.float().permute(2, 0, 1)
         if I % 8:
             xt = nn.functional.pad(xt, (0, 8 - I % 8))                # IP = roundup(I, 8): zero pad columns
-        y = _SeqFunction.apply(self, rt, xt.contiguous(), *[p for _, p in self._trainable()])
+        y = _xy_apply(rt, self, xt.contiguous(), (T, B, self._seq["output_size"]), seed=True)      # time-major: x [T, B, IP] -> pre-activation y [T, B, O]
         act = self._ACTS[self.output_activate_function]
         if act is not None:
             y = act(y)
@@ -1325,30 +1198,6 @@ class BaseModel(nn.Module):
         _weight_init(m)
 
 
-class _FSNFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, owner, rt, noisy_mag, *params):
-        plan, ar = rt
-        B, F, T = noisy_mag.shape
-        plan.io(ar, "mag", (B, F, T)).copy_(noisy_mag)
-        plan.view(ar, "io.seed").view(torch.int32)[:1].add_(1)        # fresh dropout masks every forward (device-side counter)
-        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
-        plan.stamp = getattr(plan, "stamp", 0) + 1
-        ctx.owner, ctx.rt, ctx.shape, ctx.stamp = owner, rt, (B, F, T), plan.stamp
-        return plan.io(ar, "crm", (B, F, T, 2)).clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        plan, ar = ctx.rt
-        if ctx.stamp != plan.stamp:
-            raise RuntimeError("sefd: a later forward of the same shape overwrote the activations this backward needs")
-        B, F, T = ctx.shape
-        plan.io(ar, "grad_crm", (B, F, T, 2)).copy_(g)
-        plan.run(PHASE_BWD, ar, torch.cuda.current_stream().cuda_stream)
-        flat = ctx.owner._flat_grad.clone()
-        return (None, None, None) + tuple(flat[off:off + n].view(shape) for (off, n, shape) in ctx.owner._param_slices)
-
-
 class FullSubNet(_SefdModule, BaseModel):
     """Same constructor as the reference (models.py:569-581); a BaseModel, as there (its unfold and norms run inside the fused plan)."""
 
@@ -1379,21 +1228,9 @@ class FullSubNet(_SefdModule, BaseModel):
             self._flatten(device)
         keep = self.dropout_keep if self.training else 1.0
         nb = getattr(self, "_grad_buckets", 1)
-        key = ("fsn", B, T, bool(self.training), keep, self.act_dtype, nb)
-        rt = self._runtimes.get(key)
-        if rt is None:
-            plan = Plan(B, T, fft_len=2 * (self.num_freqs - 1), act_dtype=self.act_dtype, training=True, model="FullSubNet",
-                        fsn=dict(self._fsn, keep=keep), grad_buckets=nb)
-            plan.owner = weakref.ref(self)
-            assert [n for n, _ in self._trainable()] == list(plan.params.keys()), "parameter order differs from the plan"
-            ar = [None] * ARENA_COUNT
-            ar[ARENA_WS] = torch.zeros(max(plan.arena_bytes[ARENA_WS], 256), dtype=torch.uint8, device=device)
-            ar[ARENA_CONST] = torch.from_numpy(plan.const_image()).to(device)
-            ar[ARENA_IO] = torch.zeros(plan.arena_bytes[ARENA_IO], dtype=torch.uint8, device=device)
-            ar[ARENA_PARAM], ar[ARENA_GRAD], ar[ARENA_STATE] = self._flat_param, self._flat_grad, self._flat_state
-            rt = (plan, ar)
-            self._runtimes[key] = rt
-        return rt
+        return cached(self._runtimes, ("fsn", B, T, bool(self.training), keep, self.act_dtype, nb), lambda: Runtime.bound(
+            Plan(B, T, fft_len=2 * (self.num_freqs - 1), act_dtype=self.act_dtype, training=True, model="FullSubNet",
+                 fsn=dict(self._fsn, keep=keep), grad_buckets=nb), self, device))
 
     def forward(self, noisy_mag):
         """models.py:626-672: noisy_mag [B, F, T] (or [B, 1, F, T]) -> cRM [B, F, T, 2]."""
@@ -1405,7 +1242,7 @@ class FullSubNet(_SefdModule, BaseModel):
         noisy_mag = noisy_mag.detach().float().contiguous()
         B, F, T = noisy_mag.shape
         rt = self._fsn_runtime(B, T, noisy_mag.device)
-        return _FSNFunction.apply(self, rt, noisy_mag, *[p for _, p in self._trainable()])
+        return _plan_apply(rt, self, (noisy_mag,), [rt.io("mag", (B, F, T))], [rt.io("crm", (B, F, T, 2))], [rt.io("grad_crm", (B, F, T, 2))], seed=True)
 
     def loss(self, estimated, target):
         """models.py:674-682: the four losses over the LAST axis (the real / imaginary pair of the [B, F, T, 2] masks)."""
@@ -1429,12 +1266,12 @@ class FullSubNet(_SefdModule, BaseModel):
         B, F, T = noisy_mag.shape
         # data parallel: two gradient buckets - the full-band model's range is final while the sub-band weight gradients still run (ddp.py)
         self._grad_buckets = 2 if (exchange is not None and exchange.active) else 1
-        plan, ar = self._fsn_runtime(B, T, noisy_mag.device)
+        plan, ar = rt = self._fsn_runtime(B, T, noisy_mag.device)
         plan.tolerate_fault = exchange is not None and exchange.active
         optimizer.bind(self)
         stream = torch.cuda.current_stream().cuda_stream
         plan.io(ar, "mag", (B, F, T)).copy_(noisy_mag)
-        plan.view(ar, "io.seed").view(torch.int32)[:1].add_(1)
+        _next_dropout_seed(rt)
         plan.run(PHASE_FWD, ar, stream)
         kind = tfl.LOSS_KINDS[loss_kind or cfg.loss]
         prev_dp = tfl.set_data_parallel(exchange)            # SI-SDR: mean of the row ratios over ALL ranks' rows inside the log
@@ -1457,18 +1294,6 @@ class FullSubNet(_SefdModule, BaseModel):
             plan.run_cb(PHASE_BWD, ar, stream, op, lambda: exchange.begin(self._flat_grad[lo:hi]))
         else:
             plan.run(PHASE_BWD, ar, stream)
-        if exchange is not None and exchange.active:
-            optimizer.nan_guard = self._dp_guard = self._flat_grad[-1:]          # in the last bucket, see _SefdModule.train_step
-            plan.status_poison(optimizer.nan_guard, stream)
-            if bucket is not None:
-                for a, z in ((0, bucket[1]), (bucket[2], self._flat_grad.numel())):
-                    if z > a:
-                        exchange.begin(self._flat_grad[a:z])
-                exchange.finish(self._flat_grad)
-            else:
-                exchange.all_reduce(self._flat_grad)
-            optimizer.grad_scale = exchange.grad_scale
-        optimizer.step_flat()
-        if exchange is not None and exchange.active:
-            _dp_guard_tick(self)
+        rest = None if bucket is None else [self._flat_grad[a:z] for a, z in ((0, bucket[1]), (bucket[2], self._flat_grad.numel())) if z > a]
+        _finish_step(self, plan, optimizer, exchange, stream, self._flat_grad[-1:], rest)      # the guard: in the last bucket, see _finish_step
         return loss

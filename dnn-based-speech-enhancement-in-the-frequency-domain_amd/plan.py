@@ -198,14 +198,15 @@ class Plan:
         return np.ctypeslib.as_array((C.c_uint8 * n).from_address(self.lib.sefd_plan_const_data(self.h))).copy()
 
     # ---- arenas
-    def alloc_arenas(self, device):
-        """uint8 tensors for every arena (PARAM/GRAD/STATE as float32). CONST is filled from the host image."""
+    def alloc_arenas(self, device, flat=None):
+        """uint8 tensors for every arena (PARAM/GRAD/STATE as float32). CONST is filled from the host image.
+        flat: the (PARAM, GRAD, STATE) tensors of the module that owns the parameters, bound in place of fresh ones."""
         dev = torch.device(device)
         ar = [None] * ARENA_COUNT
         ar[ARENA_WS] = torch.zeros(max(self.arena_bytes[ARENA_WS], 256), dtype=torch.uint8, device=dev)
-        ar[ARENA_PARAM] = torch.zeros(self.arena_bytes[ARENA_PARAM] // 4, dtype=torch.float32, device=dev)
-        ar[ARENA_GRAD] = torch.zeros(self.arena_bytes[ARENA_GRAD] // 4, dtype=torch.float32, device=dev)
-        ar[ARENA_STATE] = torch.zeros(self.arena_bytes[ARENA_STATE] // 4, dtype=torch.float32, device=dev)
+        if flat is None:
+            flat = [torch.zeros(self.arena_bytes[a] // 4, dtype=torch.float32, device=dev) for a in (ARENA_PARAM, ARENA_GRAD, ARENA_STATE)]
+        ar[ARENA_PARAM], ar[ARENA_GRAD], ar[ARENA_STATE] = flat
         ar[ARENA_CONST] = torch.from_numpy(self.const_image()).to(dev)
         ar[ARENA_IO] = torch.zeros(self.arena_bytes[ARENA_IO], dtype=torch.uint8, device=dev)
         return ar

@@ -10,6 +10,7 @@ import torch
 from . import _lib
 from . import config as cfg
 from .plan import PHASE_FWD, Plan
+from .runtime import Runtime, cached
 
 
 def __getattr__(name):
@@ -43,12 +44,8 @@ def _wants_grad(*tensors):
 
 
 def _fe_runtime(key, make):
-    fe = _FE_CACHE.get(key)
-    if fe is None:
-        plan = make()
-        fe = (plan, plan.alloc_arenas(key[-1]))
-        _FE_CACHE[key] = fe
-    return fe
+    """Runtime of the parameter-free plan `make()`, cached per shape; the device is the key's last element."""
+    return cached(_FE_CACHE, key, lambda: Runtime.owned(make(), key[-1]))
 
 
 class _StftFunction(torch.autograd.Function):
@@ -67,11 +64,11 @@ class _StftFunction(torch.autograd.Function):
         n_fft, hop, win = ctx.geom
         B, F, T, _ = g.shape
         L = ctx.L
-        plan, ar = _fe_runtime(("stft_adj", B, L, n_fft, hop, win, str(g.device)),
-                               lambda: Plan(B, L, win_len=win, win_inc=hop, fft_len=n_fft, model="TorchSTFTAdj"))
-        plan.io(ar, "grad_spec", (B, F, T, 2)).copy_(g)
-        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
-        return plan.io(ar, "grad_wav", (B, L)).clone(), None, None, None
+        rt = _fe_runtime(("stft_adj", B, L, n_fft, hop, win, str(g.device)),
+                         lambda: Plan(B, L, win_len=win, win_inc=hop, fft_len=n_fft, model="TorchSTFTAdj"))
+        rt.io("grad_spec", (B, F, T, 2)).copy_(g)
+        rt.run(PHASE_FWD)
+        return rt.io("grad_wav", (B, L)).clone(), None, None, None
 
 
 class _IstftFunction(torch.autograd.Function):
@@ -89,11 +86,11 @@ class _IstftFunction(torch.autograd.Function):
         n_fft, hop, win = ctx.geom
         B, F, T, _ = ctx.fshape
         L = g.shape[1]
-        plan, ar = _fe_runtime(("istft_adj", B, L, T, n_fft, hop, win, str(g.device)),
-                               lambda: Plan(B, L, win_len=win, win_inc=hop, fft_len=n_fft, model="TorchISTFTAdj"))
-        plan.io(ar, "grad_wav", (B, L)).copy_(g)
-        plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
-        return plan.io(ar, "grad_spec", (B, F, T, 2)).clone(), None, None, None, None
+        rt = _fe_runtime(("istft_adj", B, L, T, n_fft, hop, win, str(g.device)),
+                         lambda: Plan(B, L, win_len=win, win_inc=hop, fft_len=n_fft, model="TorchISTFTAdj"))
+        rt.io("grad_wav", (B, L)).copy_(g)
+        rt.run(PHASE_FWD)
+        return rt.io("grad_spec", (B, F, T, 2)).clone(), None, None, None, None
 
 
 def stft(y, n_fft=cfg.fft_len, hop_length=int(cfg.win_len * cfg.ola_ratio), win_length=cfg.win_len):
@@ -108,16 +105,11 @@ def stft(y, n_fft=cfg.fft_len, hop_length=int(cfg.win_len * cfg.ola_ratio), win_
         return torch.view_as_complex(_StftFunction.apply(y.float().contiguous(), n_fft, hop_length, win_length))
     y = y.detach().float().contiguous()
     B, L = y.shape
-    key = (B, L, n_fft, hop_length, win_length, str(y.device))
-    fe = _FE_CACHE.get(key)
-    if fe is None:
-        plan = Plan(B, L, win_len=win_length, win_inc=hop_length, fft_len=n_fft, model="TorchSTFT")
-        fe = (plan, plan.alloc_arenas(y.device))
-        _FE_CACHE[key] = fe
-    plan, ar = fe
-    plan.io(ar, "wav", (B, L)).copy_(y)
-    plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
-    return torch.view_as_complex(plan.io(ar, "spec", (B, plan.NF, plan.T, 2)).clone())
+    rt = _fe_runtime((B, L, n_fft, hop_length, win_length, str(y.device)),
+                     lambda: Plan(B, L, win_len=win_length, win_inc=hop_length, fft_len=n_fft, model="TorchSTFT"))
+    rt.io("wav", (B, L)).copy_(y)
+    rt.run(PHASE_FWD)
+    return torch.view_as_complex(rt.io("spec", (B, rt.plan.NF, rt.plan.T, 2)).clone())
 
 
 def istft(features, n_fft=cfg.fft_len, hop_length=int(cfg.win_len * cfg.ola_ratio), win_length=cfg.win_len, length=None, use_mag_phase=False):
@@ -139,18 +131,16 @@ def istft(features, n_fft=cfg.fft_len, hop_length=int(cfg.win_len * cfg.ola_rati
         # every entry form arrives here as the real pair through differentiable torch ops (view_as_real; mag x (cos, sin), whose autograd is the polar adjoint)
         return _IstftFunction.apply(features.float().contiguous(), n_fft, hop_length, win_length, L)
     features = features.detach().float().contiguous()
-    key = ("istft", B, L, T, n_fft, hop_length, win_length, str(features.device))
-    fe = _FE_CACHE.get(key)
-    if fe is None:
+
+    def make():
         plan = Plan(B, L, win_len=win_length, win_inc=hop_length, fft_len=n_fft, model="TorchISTFT")
         if plan.T != T:
             raise ValueError(f"istft: {T} frames do not match length {L} at hop {hop_length} (expected {plan.T})")
-        fe = (plan, plan.alloc_arenas(features.device))
-        _FE_CACHE[key] = fe
-    plan, ar = fe
-    plan.io(ar, "spec", (B, F, T, 2)).copy_(features)
-    plan.run(PHASE_FWD, ar, torch.cuda.current_stream().cuda_stream)
-    return plan.io(ar, "wav", (B, L)).clone()
+        return plan
+    rt = _fe_runtime(("istft", B, L, T, n_fft, hop_length, win_length, str(features.device)), make)
+    rt.io("spec", (B, F, T, 2)).copy_(features)
+    rt.run(PHASE_FWD)
+    return rt.io("wav", (B, L)).clone()
 
 
 def _targets(noisy, clean, want_mag, want_phase, want_cirm):

@@ -157,3 +157,23 @@ def test_validate_and_eval_mode_with_the_knobs(tmp_path):
         m.eval()
         crm_eval = m(noisy_mag).clone()
     assert float(crm_train.abs().max()) > 0 and float(crm_train.abs().max()) <= 1.0 and torch.equal(crm_train, crm_eval)
+
+
+def test_stale_backward_is_refused():
+    """A forward of the same shape between a forward and its backward overwrites the activations in the runtime's arena: that backward raises; a
+    fresh forward and backward reach the parameters (the input is detached)."""
+    import sefd_amd  # noqa: F401
+    from sefd_amd import config as cfg, models
+    cfg.loss, cfg.act_dtype = "MSE", "fp32"
+    m = models.FullSubNet(sb_num_neighbors=2, fb_num_neighbors=2, fb_model_hidden_size=16, sb_model_hidden_size=16)
+    fill_state_dict_(m)
+    m = m.to("cuda").train()
+    mag = torch.rand(1, 257, 4, generator=torch.Generator().manual_seed(5)).cuda() + 0.1
+    crm = m(mag)
+    m(mag)
+    with pytest.raises(RuntimeError, match="overwrote the activations"):
+        (crm ** 2).sum().backward()
+    m.zero_grad()
+    (m(mag) ** 2).sum().backward()
+    g = m.sb_model.fc_output_layer.weight.grad
+    assert g is not None and bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0

@@ -1032,3 +1032,25 @@ def test_direct_mapping_fused_step_equals_autograd_route(which, loss_kind):
         if pa[k].dtype.is_floating_point:
             assert float((pa[k] - pb[k]).abs().max()) <= 1e-5 * max(1.0, float(pa[k].abs().max())), k
     cfg.masking_mode, cfg.loss = "E", "SI-SNR"
+
+
+def test_stale_backward_is_refused_and_missing_cotangents_are_zero_filled():
+    """DCCRN at [1, 1600]: a forward of the same shape between a forward and its backward overwrites the activations in the runtime's arena - that
+    backward raises.  Fresh passes: a loss on out_wav alone (out_real / out_imag get no cotangent: their gradient buffers are zero-filled), then one
+    on out_real alone; both reach the first encoder layer's weight with a finite, non-zero gradient."""
+    m = make_model((16, 32, 32, 64, 64, 64), 64, "E", "SI-SNR").train()
+    x, _ = make_signals(1, 1600)
+    x = x.cuda()
+    w = m.encoder[0][0].real_conv.weight
+    _, _, wav = m(x)
+    m(x)
+    with pytest.raises(RuntimeError, match="before the next forward"):
+        (wav ** 2).sum().backward()
+    grads = []
+    for pick in (2, 0):                     # out_wav alone, out_real alone
+        m.zero_grad()
+        (m(x)[pick] ** 2).sum().backward()
+        g = w.grad.detach().clone()
+        assert bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0, pick
+        grads.append(g)
+    assert not torch.equal(grads[0], grads[1])

@@ -219,3 +219,16 @@ def test_cpu_tensor_is_rejected_not_silently_computed():
     m = make_model("LSTM", 21, 5, 64, 1, False, None)
     with pytest.raises(RuntimeError, match="cuda"):
         m(torch.zeros(2, 21, 4))
+
+
+def test_stale_backward_is_refused():
+    """A forward of the same shape between a forward and its backward overwrites the activations in the runtime's arena: that backward raises; a
+    fresh forward and backward reach the input."""
+    m = make_model("LSTM", 5, 3, 16, 1, False, None)
+    x = torch.randn(2, 5, 3, generator=torch.Generator().manual_seed(3)).cuda().requires_grad_(True)
+    y = m(x)
+    m(x)
+    with pytest.raises(RuntimeError, match="overwrote the activations"):
+        (y ** 2).sum().backward()
+    (m(x) ** 2).sum().backward()
+    assert bool(torch.isfinite(x.grad).all()) and float(x.grad.abs().max()) > 0
