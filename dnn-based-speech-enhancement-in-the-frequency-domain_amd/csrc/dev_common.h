@@ -204,7 +204,9 @@ int rungemm_persist_grid(const RunGemm& d);                                     
 // The kernel family launch_rungemm picks for a RUNGEMM descriptor under the knobs of the moment (sefd_plan_op_info reports it)
 bool launch_thin_mask(const RunGemm& d, const ArenaBases& ab, hipStream_t st);       // frame-staged mask-layer conv and its input gradient (thin_mask.hip)
 int thin_mask_grid(const RunGemm& d);                                                // ... its grid; 0: `d` stays where it was
-enum RunFamily : int { kFamNone = 0, kFamEnc0 = 1, kFamCgemm256 = 2, kFamDirect = 3, kFamTiled = 4, kFamPersist = 5, kFamThinMask = 6 };
+bool launch_thin_stage(const RunGemm& d, const ArenaBases& ab, hipStream_t st);      // frame-staged phase-merged thin layers: dec4 forward, enc1 input gradient (thin_stage.hip)
+int thin_stage_grid(const RunGemm& d);                                               // ... its grid; 0: `d` stays where it was
+enum RunFamily : int { kFamNone = 0, kFamEnc0 = 1, kFamCgemm256 = 2, kFamDirect = 3, kFamTiled = 4, kFamPersist = 5, kFamThinMask = 6, kFamThinStage = 7 };
 int rungemm_family(const RunGemm& d);
 void launch_misc(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st);

@@ -10,7 +10,7 @@ from . import _lib
 ARENA_WS, ARENA_PARAM, ARENA_GRAD, ARENA_STATE, ARENA_CONST, ARENA_IO, ARENA_COUNT = 0, 1, 2, 3, 4, 5, 6
 PHASE_FWD, PHASE_BWD = 0, 1
 # op_info()["family"] of a RUNGEMM op (csrc/dev_common.h RunFamily)
-RUN_FAMILY_NONE, RUN_FAMILY_ENC0, RUN_FAMILY_CGEMM256, RUN_FAMILY_DIRECT, RUN_FAMILY_TILED, RUN_FAMILY_PERSIST, RUN_FAMILY_THIN_MASK = range(7)
+RUN_FAMILY_NONE, RUN_FAMILY_ENC0, RUN_FAMILY_CGEMM256, RUN_FAMILY_DIRECT, RUN_FAMILY_TILED, RUN_FAMILY_PERSIST, RUN_FAMILY_THIN_MASK, RUN_FAMILY_THIN_STAGE = range(8)
 RUN_WAVE_ONLY = 1
 MASK_MODES = {"E": 0, "C": 1, "R": 2, "Direct(None make)": 4}
 DTYPES = {"fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
