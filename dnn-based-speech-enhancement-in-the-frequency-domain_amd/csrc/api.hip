@@ -111,7 +111,8 @@ int32_t sefd_plan_op_info(const sefd_plan* h, int phase, int i, int64_t* o) {
     int64_t K = 0;
     for (int s = 0; s < g.nseg; ++s) K += g.seg[s].len;
     o[2] = g.M; o[3] = g.N; o[4] = K; o[5] = g.xdt | ((int64_t)(uint32_t)g.flags << 8);   // low byte: operand dtype; bits 8-39: RunGemm flags
-    if (op.kind == OP_RUNGEMM) o[5] |= (int64_t)rungemm_family(g) << 48;                  // bits 48-55: the kernel family a launch would pick now (dev_common.h RunFamily)
+    // bits 48-55: the kernel family a launch would pick now (dev_common.h RunFamily / WgradFamily)
+    o[5] |= (int64_t)(op.kind == OP_RUNGEMM ? rungemm_family(g) : wgrad_family(g)) << 48;
     o[6] = 2 * (int64_t)g.M * g.N * K;                                     // algorithmic flops (true K, true N)
     // algorithmic bytes: every source element once is not well defined for overlapping runs; report A-row + y + w traffic
     o[7] = (int64_t)g.M * g.N * esize(g.ydt) + (int64_t)g.N * K * esize(g.xdt);

@@ -208,6 +208,12 @@ bool launch_thin_stage(const RunGemm& d, const ArenaBases& ab, hipStream_t st); 
 int thin_stage_grid(const RunGemm& d);                                               // ... its grid; 0: `d` stays where it was
 enum RunFamily : int { kFamNone = 0, kFamEnc0 = 1, kFamCgemm256 = 2, kFamDirect = 3, kFamTiled = 4, kFamPersist = 5, kFamThinMask = 6, kFamThinStage = 7 };
 int rungemm_family(const RunGemm& d);
+// ... and the kernel launch_wgrad picks for a WGRAD descriptor (reported in the same bits): first layer on the spectrum, plain or with the BatchNorm backward
+// fused (enc0.hip); rank-N streaming kernel; LDS-DMA kernel as 256 x 256 tile, 256 x 256 with the bias from the ones MFMA, 128 x 512 tile, 128 / 64 / 32 wide
+// n tiles; register-staged bf16 kernel, 128 / 64 wide; fp32 kernel
+enum WgradFamily : int { kWgFamNone = 0, kWgFamEnc0 = 1, kWgFamEnc0Fused = 2, kWgFamRank = 3, kWgFamWide256 = 4, kWgFamWide256Ones = 5, kWgFamWide128 = 6,
+                         kWgFamDma128 = 7, kWgFamDma64 = 8, kWgFamDma32 = 9, kWgFamBf16_128 = 10, kWgFamBf16_64 = 11, kWgFamF32 = 12 };
+int wgrad_family(const RunGemm& d);
 void launch_misc(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st);
 void launch_istft_fft(const IstftFft& d, const ArenaBases& ab, hipStream_t st);

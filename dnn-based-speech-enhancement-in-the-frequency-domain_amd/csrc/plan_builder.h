@@ -826,6 +826,10 @@ struct Builder {
       g.flags |= kRunRank;
       ns = std::max(1, std::min(1024, steps / 4));
     }
+    // WG_NSPLIT = n > 0 (tests): min(n, steps) row splits for EVERY weight gradient of the plan, whatever its kernel - 1: one workgroup per tile walks every
+    // row of every batch item; a huge n: one 32-row step per split.  The partial sums and the SPLITSUM table below are sized from it.  0 / unset: the rule above
+    const int64_t ns_forced = tune_int("WG_NSPLIT", 0);
+    if (ns_forced > 0) ns = (int)std::max<int64_t>(1, std::min<int64_t>(ns_forced, steps));
     g.nsplit = ns;
     const int64_t sz = (int64_t)g.Npad * g.ldw;
     const int64_t rel = gp_off;

@@ -1346,8 +1346,7 @@ void launch_wgrad(const RunGemm& d0, const ArenaBases& ab, hipStream_t st) {
     switch (wgrad_tn(d.xdt, d.N, d.Npad)) {        // sefd_desc.h: the planner sized nsplit for the same tile
       case 128: launch_wgrad_dma<128>(d, ab, st); break;
       case 64: launch_wgrad_dma<64>(d, ab, st); break;
-      case 32: launch_wgrad_dma<32>(d, ab, st); break;
-      default: launch_wgrad_dma<16>(d, ab, st); break;
+      default: launch_wgrad_dma<32>(d, ab, st); break;   // (wgrad_tn returns 32, 64 or 128)
     }
     return;
   }
@@ -1363,6 +1362,23 @@ void launch_wgrad(const RunGemm& d0, const ArenaBases& ab, hipStream_t st) {
   }
   dim3 grid(((d.Npad + kWgTN - 1) / kWgTN) * ((d.ldw + kWgTK - 1) / kWgTK) * d.nsplit);
   hipLaunchKernelGGL((wgrad_kernel<float>), grid, dim3(256), 0, st, d, ab);
+}
+
+// The same decisions as launch_wgrad, without a launch (sefd_plan_op_info)
+int wgrad_family(const RunGemm& d) {
+  if ((d.flags & kRunEnc0) && enc0_accepts(d, true)) return (d.flags & kRunDyFromBn) ? kWgFamEnc0Fused : kWgFamEnc0;
+  if (d.flags & (kRunEnc0 | kRunDyFromBn)) return kWgFamNone;
+  if ((d.flags & kRunRank) && wgrad_rank_form(d)) return kWgFamRank;
+  if (d.xdt == DT_BF16 && (d.flags & kRunAligned)) {
+    if (d.flags & kRunWgWide) return d.Npad % 256 != 0 ? kWgFamWide128 : (d.flags & kRunOnesMfma) ? kWgFamWide256Ones : kWgFamWide256;
+    switch (wgrad_tn(d.xdt, d.N, d.Npad)) {
+      case 128: return kWgFamDma128;
+      case 64: return kWgFamDma64;
+      default: return kWgFamDma32;
+    }
+  }
+  if (d.xdt == DT_BF16) return d.Npad >= 128 ? kWgFamBf16_128 : kWgFamBf16_64;
+  return kWgFamF32;
 }
 
 }  // namespace sefd

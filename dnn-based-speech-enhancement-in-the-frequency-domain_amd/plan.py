@@ -11,6 +11,13 @@ ARENA_WS, ARENA_PARAM, ARENA_GRAD, ARENA_STATE, ARENA_CONST, ARENA_IO, ARENA_COU
 PHASE_FWD, PHASE_BWD = 0, 1
 # op_info()["family"] of a RUNGEMM op (csrc/dev_common.h RunFamily)
 RUN_FAMILY_NONE, RUN_FAMILY_ENC0, RUN_FAMILY_CGEMM256, RUN_FAMILY_DIRECT, RUN_FAMILY_TILED, RUN_FAMILY_PERSIST, RUN_FAMILY_THIN_MASK, RUN_FAMILY_THIN_STAGE = range(8)
+# ... of a WGRAD op (csrc/dev_common.h WgradFamily): the first layer on the spectrum, plain / with the BatchNorm backward fused; the rank-N streaming kernel;
+# the LDS-DMA kernel as 256 x 256 tile, 256 x 256 with the bias from the ones MFMA, 128 x 512 tile and 128 / 64 / 32 wide n tiles; the register-staged bf16
+# kernel (unaligned runs), 128 / 64 wide; the fp32 kernel
+(WG_FAMILY_NONE, WG_FAMILY_ENC0, WG_FAMILY_ENC0_FUSED, WG_FAMILY_RANK, WG_FAMILY_WIDE256, WG_FAMILY_WIDE256_ONES, WG_FAMILY_WIDE128,
+ WG_FAMILY_DMA128, WG_FAMILY_DMA64, WG_FAMILY_DMA32, WG_FAMILY_BF16_128, WG_FAMILY_BF16_64, WG_FAMILY_F32) = range(13)
+WG_FAMILY_NAMES = ("none", "first layer", "first layer fused", "rank-N", "256 x 256", "256 x 256 ones MFMA", "128 x 512", "aligned 128", "aligned 64",
+                   "aligned 32", "unaligned bf16 128", "unaligned bf16 64", "fp32")
 RUN_WAVE_ONLY = 1
 MASK_MODES = {"E": 0, "C": 1, "R": 2, "Direct(None make)": 4}
 DTYPES = {"fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -176,8 +183,8 @@ class Plan:
         return raw[:, 0].copy(), raw[:, 1].copy()
 
     def op_info(self, phase, i):
-        """dict(kind, tag, M, N, K, dtype, flags, family, flops, bytes) of op i (RUNGEMM / WGRAD carry the GEMM geometry).  family (RUNGEMM): the
-        kernel a launch would pick under the tuning table of the moment - one of the RUN_FAMILY_* values below."""
+        """dict(kind, tag, M, N, K, dtype, flags, family, flops, bytes) of op i (RUNGEMM / WGRAD carry the GEMM geometry).  family: the kernel a
+        launch would pick under the tuning table of the moment - one of the RUN_FAMILY_* (RUNGEMM) / WG_FAMILY_* (WGRAD) values above."""
         o = (C.c_int64 * 8)()
         if self.lib.sefd_plan_op_info(self.h, phase, i, o) != 0:
             raise IndexError(i)

@@ -61,6 +61,9 @@ TABLE = [
     # ---- CRN (real convs over kernel_num / 2 channels): 8, 24, 40, 72, 136 channels in five layers (D = 8), and fft_len 256
     Entry("crn5", "CRN", 2, 3000, dict(kernel_num=(16, 48, 80, 144, 272), rnn_units=64), BOTH),
     Entry("crn_fft256", "CRN", 2, 2000, dict(kernel_num=SMALL_KN, rnn_units=64, fft_len=256, win_len=200, win_inc=50), BOTH),
+    # CRN at the default channels under the wide-tile knobs: 128 real channels with K >= 1024 packed columns (tags 104, 105, 400, 401) - the 128 x 512
+    # weight-gradient tile, which no DCCRN layer takes (its N = 128 layers have 640 columns)
+    Entry("crn_wide", "CRN", 2, 2400, dict(kernel_num=(32, 64, 128, 256, 256, 256), rnn_units=256), ("bf16",), WIDE),
     Entry("crn3", "CRN", 1, 2000, dict(kernel_num=(16, 48, 80), rnn_units=64), F32),                # D = 32: four chunks of channel slices
     # CRN halves cfg.dccrn_kernel_num: (8, 24, 40, 72, 136) would be 4, 12, 20, 36, 68 real channels, not multiples of 8
     Entry("crn_odd_refused", "CRN", 2, 3000, dict(kernel_num=(8, 24, 40, 72, 136), rnn_units=64), BOTH, (), "channel counts must be multiples of 8"),

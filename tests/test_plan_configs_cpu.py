@@ -9,6 +9,7 @@ import torch
 from plan_check import check_crn_plan_vs_oracle, check_dccrn_plan_vs_oracle
 from plan_configs import ACCEPTED, TABLE, entry_id, plan_kwargs
 from simutil import PHASE_BWD, PHASE_FWD, Plan, sim
+from sefd_amd.plan import WG_FAMILY_WIDE128, WG_FAMILY_WIDE256, WG_FAMILY_WIDE256_ONES
 from util import knobs
 
 KIND_RUNGEMM, KIND_WGRAD, KIND_STFT_FFT = 1, 2, 37          # sefd_desc.h OpKind
@@ -141,8 +142,11 @@ def test_table_reaches_every_descriptor_class():
                     hit("thin-eligible RUNGEMM under DIRECT_MINM=0 (thin.hip)", e, dtype, g)
                 if run and g["flags"] & RUN_WTILE32:
                     hit("wide-tile RUNGEMM, Npad % 256 == 0 (cgemm256.hip)", e, dtype, g)
-                if wg and g["flags"] & RUN_WG_WIDE:
-                    hit("wide-tile WGRAD (256 x 256 tile)", e, dtype, g)
+                if wg and g["flags"] & RUN_WG_WIDE:                   # launch_wgrad: Npad % 256 == 0 -> launch_wgrad_wide, else launch_wgrad_wide128
+                    wide256 = g["Npad"] % 256 == 0
+                    assert g["family"] in ((WG_FAMILY_WIDE256, WG_FAMILY_WIDE256_ONES) if wide256 else (WG_FAMILY_WIDE128,)), (e.name, g)
+                    assert wide256 or (g["Npad"] == 128 and g["ldw"] >= 1024), (e.name, g)
+                    hit("wide-tile WGRAD (256 x 256 tile)" if wide256 else "wide-tile WGRAD (128 x 512 tile)", e, dtype, g)
                 if bf16 and conv and g["Npad"] == 384 and dict(e.knobs).get("CG256_MINM"):
                     hit("Npad = 384 beside the wide tiles (128-wide kernels)", e, dtype, g)
                 if wg and bf16 and g["dtype"] == 1:
@@ -156,7 +160,7 @@ def test_table_reaches_every_descriptor_class():
     want = ["Npad > N (tile tail in N)", "bn_of(N) = 32", "bn_of(N) = 64", "bn_of(N) = 128",
             "bf16 RUNGEMM without kRunAligned (non-DMA rungemm_kernel)", "bf16 WGRAD without kRunAligned (wgrad_bf16_kernel<64 / 128>)",
             "bf16 RUNGEMM without kRunYAligned (non-staged epilogue)", "thin-eligible RUNGEMM under DIRECT_MINM=0 (thin.hip)",
-            "wide-tile RUNGEMM, Npad % 256 == 0 (cgemm256.hip)", "wide-tile WGRAD (256 x 256 tile)", "Npad = 384 beside the wide tiles (128-wide kernels)",
+            "wide-tile RUNGEMM, Npad % 256 == 0 (cgemm256.hip)", "wide-tile WGRAD (256 x 256 tile)", "wide-tile WGRAD (128 x 512 tile)", "Npad = 384 beside the wide tiles (128-wide kernels)",
             "wgrad_tn = 32", "wgrad_tn = 64", "wgrad_tn = 128", "framing-GEMM STFT (no OP_STFT_FFT)", "bf16 first layer without kRunEnc0",
             "recurrent input GEMM in chunks of 8 channel slices (kRunAccum)", "bias-only WGRAD behind a full run list (D >= 8)"]
     for name in want:
