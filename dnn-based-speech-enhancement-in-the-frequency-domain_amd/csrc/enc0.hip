@@ -115,9 +115,12 @@ __global__ __launch_bounds__(256) void enc0_fwd_kernel(const RunGemm d, const Ar
       }
     }
     __syncthreads();                                         // the frame's sums are in LDS; every wave is done with ring slot `prv` (refilled next)
-    if (part && tid < d.N) {                                 // one row of partial sums per 128 output rows = this frame; waves added in order
-      const float a1 = st[t & 1][0][tid][0] + st[t & 1][1][tid][0] + st[t & 1][2][tid][0] + st[t & 1][3][tid][0];
-      const float a2 = st[t & 1][0][tid][1] + st[t & 1][1][tid][1] + st[t & 1][2][tid][1] + st[t & 1][3][tid][1];
+    if (part && tid < d.Npad) {                              // one row of partial sums per 128 output rows = this frame; waves added in order
+      // the rows are Npad wide and the launch owns all of them (sefd_desc.h RunGemm::stats): the pad columns are written as zero, as rungemm_kernel
+      // and the host simulator write them
+      const bool col = tid < d.N;
+      const float a1 = col ? st[t & 1][0][tid][0] + st[t & 1][1][tid][0] + st[t & 1][2][tid][0] + st[t & 1][3][tid][0] : 0.f;
+      const float a2 = col ? st[t & 1][0][tid][1] + st[t & 1][1][tid][1] + st[t & 1][2][tid][1] + st[t & 1][3][tid][1] : 0.f;
       const int64_t blk = (int64_t)b * T + t;
       part[(blk * 2 + 0) * d.Npad + tid] = a1;
       part[(blk * 2 + 1) * d.Npad + tid] = a2;

@@ -88,6 +88,37 @@ def conv_inputs(name, seed=SEED):
     return dict(x=_u(8000 + 16 * seed, (B, ci, F, T)), cot=_u(8001 + 16 * seed, (B, co, Fo, To)))
 
 
+# The integer variant of the bf16 plans' cases (convlayer_<name>_int.npz): x and the cotangent integers in -3 .. 3, every weight and bias an integer in
+# -1 .. 1.  Every y, dx and parameter gradient is then an integer far below 2^24: float32 and float64 give the same numbers, in any order of additions,
+# and a bf16 plan must give y and dx rounded to bf16 and the parameter gradients themselves, exactly.
+INT_CASES = ("enc_mid", "odd_ch", "k3s1", "t_dec", "t_mask", "r_dec")
+
+
+def _ints(idx, shape, hi):
+    """Integers uniform in -hi .. hi from splitmix stream `idx`, as float32."""
+    u = splitmix_uniform(idx, int(np.prod(shape)))
+    v = np.minimum(np.floor((u + 1.0) * (hi + 0.5)), 2 * hi) - hi
+    return torch.from_numpy(np.ascontiguousarray(v.reshape(shape), dtype=np.float32))
+
+
+def int_inputs(name, seed=SEED):
+    cls, ci, co, k, s, p, extra, F, T = CASES[name]
+    Fo, To = out_geometry(name)
+    return dict(x=_ints(8007 + 16 * seed, (B, ci, F, T), 3), cot=_ints(8008 + 16 * seed, (B, co, Fo, To), 3))
+
+
+def fill_int_(module, seed):
+    with torch.no_grad():
+        for i, (n, t) in enumerate(module.named_parameters()):
+            t.copy_(_ints(9500 + 64 * seed + i, tuple(t.shape), 1).to(device=t.device, dtype=t.dtype))
+
+
+def load_int_golden(name):
+    """({"y", "dx", "d/<parameter>": tensor of integers, float32}, seed) of an integer case."""
+    z = np.load(os.path.join(GOLDEN, f"convlayer_{name}_int.npz"))
+    return {k[4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("ref/")}, int(z["seed"])
+
+
 def cbn_inputs(name, seed=SEED):
     C, rest, _, _ = CBN_CASES[name]
     shape = (B, C) + tuple(rest)

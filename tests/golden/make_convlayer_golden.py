@@ -6,6 +6,11 @@ y = f(x), loss = sum(y * cot), backward.  Inputs, cotangents and parameter value
 stored seed: convlayer_common.fill_ / *_inputs), so a fixture holds the seed and the results only: every float64 output, input gradient,
 parameter gradient and buffer after the forward, rounded to float32, and per tensor ref32_err = max|ref32 - ref64| / max|ref64|.
 
+The integer variant (convlayer_common.INT_CASES, convlayer_<name>_int.npz; `int` on the command line makes these alone): x and the cotangent integers
+in -3 .. 3, every weight and bias an integer in -1 .. 1 (convlayer_common.int_inputs / fill_int_).  Asserted here: every y, dx and parameter gradient
+is an integer far below 2^24, and the reference's float32 run equals its float64 run exactly - so the fixture is the one right answer of any kernel
+whose accumulators are at least fp32, whatever its order of additions.
+
     python tests/golden/make_convlayer_golden.py [case ...]
 """
 import os
@@ -47,10 +52,34 @@ def both(build, inp, training=True, forward_of=None):
     return res
 
 
+def write_int(tfm, name):
+    res = []
+    for dtype in (torch.float64, torch.float32):
+        m = lc.make_conv(tfm, name)
+        lc.fill_int_(m, lc.SEED)
+        res.append(lc.run_module(m.to(dtype).train(True), lc.int_inputs(name), dtype))
+    r64, r32 = res
+    rec = dict(seed=lc.SEED)
+    for k, v in r64.items():
+        assert torch.equal(v, v.round()) and float(v.abs().max()) < 2 ** 16, (name, k, float(v.abs().max()))      # integers far below 2^24
+        assert torch.equal(r32[k], v), (name, k)                                                            # float32 == float64, exactly
+        assert float(v.abs().max()) > 0, (name, k)
+        rec["ref/" + k] = v.float().numpy()
+    path = os.path.join(HERE, f"convlayer_{name}_int.npz")
+    np.savez_compressed(path, **rec)
+    assert os.path.getsize(path) < MAX_BYTES, (path, os.path.getsize(path))
+    print(f"convlayer_{name}_int: {os.path.getsize(path)} bytes, largest |value| {max(float(v.abs().max()) for v in r64.values()):.0f}")
+
+
 def main():
     _, _, tfm, _ = mg.import_reference()
     torch.set_num_threads(4)
     want = sys.argv[1:]
+    if not want or "int" in want:
+        for name in lc.INT_CASES:
+            write_int(tfm, name)
+        if want:
+            return
     e = []
     for name in lc.CASES:
         if not want or name in want:

@@ -1239,6 +1239,18 @@ extern "C" int hostsim_gemm_fields(const void* op_, int64_t* out) {
   out[0] = g.Npad; out[1] = g.ldw; out[2] = g.nseg; out[3] = g.nsplit; out[4] = g.ydt; out[5] = g.n2; out[6] = longest; out[7] = odd;
   return 0;
 }
+// test hook: the destinations of RUNGEMM / WGRAD descriptor `op_` as rungemm() above reads them (tests/exact_data.py checks its ctypes view of the
+// fields behind `flags` against this): out = {n2, y2 arena, y2 offset, stats arena, stats offset, bnb_y arena, bnb_y offset, bnb_bstride,
+// bnb_tstride, bnb_fstride, bnb_off, bnb_mi arena, bnb_mi offset, bias arena, bias offset, y offset}; -1: not such an op
+extern "C" int hostsim_gemm_tail(const void* op_, int64_t* out) {
+  const Op& op = *(const Op*)op_;
+  if (op.kind != OP_RUNGEMM && op.kind != OP_WGRAD) return -1;
+  const RunGemm& g = op.g;
+  const int64_t v[16] = {g.n2, g.y2.arena, g.y2.off, g.stats.arena, g.stats.off, g.bnb_y.arena, g.bnb_y.off, g.bnb_bstride,
+                         g.bnb_tstride, g.bnb_fstride, g.bnb_off, g.bnb_mi.arena, g.bnb_mi.off, g.bias.arena, g.bias.off, g.y.off};
+  for (int i = 0; i < 16; ++i) out[i] = v[i];
+  return 0;
+}
 // job order of the ticket-drawn recurrence launches (sefd_desc.h rows_pair_job / rows_bwd_job): out = {layer, chunk, block, tb, te}
 extern "C" void hostsim_rows_job(int bwd, int job, int nblk, int C, int T, int* out) {
   const RowsJob r = bwd ? rows_bwd_job(job, nblk, C, T) : rows_pair_job(job, nblk, C, T);

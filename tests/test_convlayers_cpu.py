@@ -200,6 +200,39 @@ def test_conv_plans_and_host_simulator(name):
         assert err < TOL, (name, key, err)
 
 
+@pytest.mark.parametrize("name", lc.INT_CASES)
+def test_bf16_conv_plans_on_integer_data_equal_the_reference_exactly(name):
+    """The anchor outside the descriptor: simulator and kernel read the same RunGemm, so a tap the planner describes wrongly is wrong on both sides.  On
+    integer data (convlayer_common.int_inputs / fill_int_) the real reference's result is exact in any arithmetic; the bf16 plan on the simulator must give
+    y and dx equal to it rounded to bf16, byte for byte, and every parameter gradient equal to it as fp32 (the GPU twin: test_gpu_convlayers.py)."""
+    from sefd_amd import models
+    cls, ci, co, k, s, p, extra, F, T = lc.CASES[name]
+    Fo, To = lc.out_geometry(name)
+    cip, cop = -(-ci // 8) * 8, -(-co // 8) * 8
+    ref, seed = lc.load_int_golden(name)
+    assert all(torch.equal(v, v.round()) and float(v.abs().max()) < 2 ** 16 for v in ref.values())
+    plan = _conv_plan(name, "bf16")
+    m = lc.make_conv(models, name)
+    lc.fill_int_(m, seed)
+    inp = lc.int_inputs(name, seed)
+    ar = plan.alloc_arenas("cpu")
+    fill_params(plan, ar, m.state_dict())
+    _to_cl(plan, ar, "x", inp["x"], cip)
+    _run_between_layout_ops(plan, PHASE_FWD, ar)
+    _to_cl(plan, ar, "dy", inp["cot"], cop)
+    _run_between_layout_ops(plan, PHASE_BWD, ar)
+    assert plan.view(ar, "y").dtype == torch.bfloat16 and plan.view(ar, "dx").dtype == torch.bfloat16
+    res = {"y": act_to_nchw(plan.view(ar, "y"), lc.B, To, Fo, cop)[:, :co], "dx": act_to_nchw(plan.view(ar, "dx"), lc.B, T, F, cip)[:, :ci]}
+    for key in ("y", "dx"):
+        got, want = res[key].to(torch.bfloat16), ref[key].to(torch.bfloat16)
+        assert torch.equal(got.float(), res[key])                    # (the buffer holds bf16 values)
+        assert torch.equal(got.view(torch.int16), want.view(torch.int16)), (name, key, int((got != want).sum()), "elements differ from the reference")
+    grads = read_params(plan, ar, ARENA_GRAD)
+    assert set(ref) == {"y", "dx"} | {"d/" + n for n in grads}
+    for n, v in grads.items():
+        assert torch.equal(v, ref["d/" + n]), (name, n, int((v != ref["d/" + n]).sum()), "elements differ from the reference")
+
+
 @pytest.mark.parametrize("name", list(lc.CBN_CASES))
 def test_cbn_plans_and_host_simulator(name):
     from sefd_amd import models

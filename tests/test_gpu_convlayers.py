@@ -11,7 +11,7 @@ import torch
 import convlayer_common as lc
 import opcheck
 from plan_check import report_path
-from simutil import ARENA_COUNT, PHASE_BWD, PHASE_FWD, Plan, fill_params, sim_run
+from simutil import ARENA_COUNT, ARENA_GRAD, PHASE_BWD, PHASE_FWD, Plan, fill_params, read_params, sim_run
 
 pytestmark = pytest.mark.gpu
 OP_NCHW_CL = 51                # sefd_desc.h OpKind
@@ -153,6 +153,41 @@ def test_bf16_conv_plans_op_by_op(name):
     lc.fill_(m, lc.SEED)
     inp = lc.conv_inputs(name)
     _ops_against_simulator(plan, m.state_dict(), (("x", inp["x"]), ("grad_y", inp["cot"])), f"convlayer_ops_{name}.txt")
+
+
+@pytest.mark.parametrize("name", lc.INT_CASES)
+def test_bf16_conv_plans_on_integer_data_equal_the_reference_exactly(name):
+    """The anchor outside the descriptor (the simulator reads the same RunGemm as the kernel): on integer data the real reference's result
+    (tests/golden/make_convlayer_golden.py, convlayer_<name>_int.npz) is exact in any arithmetic.  Both phases of the bf16 plan run whole; y and dx must
+    equal the golden rounded to bf16, byte for byte, and every parameter gradient the golden itself, as fp32 (the CPU twin, on the simulator:
+    test_convlayers_cpu.py)."""
+    from sefd_amd import models
+    cls, ci, co, k, s, p, extra, F, T = lc.CASES[name]
+    Fo, To = lc.out_geometry(name)
+    ref, seed = lc.load_int_golden(name)
+    plan = Plan(lc.B, T, act_dtype="bf16", model="ConvLayer",
+                conv=dict(kind=cls, in_channels=ci, out_channels=co, kernel_size=k, stride_f=s[0], padding=p, causal=extra.get("causal", True),
+                          output_padding_f=extra.get("output_padding", (0, 0))[0], F=F))
+    m = lc.make_conv(models, name)
+    lc.fill_int_(m, seed)
+    inp = lc.int_inputs(name, seed)
+    dev = plan.alloc_arenas("cuda")
+    fill_params(plan, dev, m.state_dict())
+    plan.io(dev, "x", tuple(inp["x"].shape)).copy_(inp["x"])
+    plan.run(PHASE_FWD, dev)
+    plan.io(dev, "grad_y", tuple(inp["cot"].shape)).copy_(inp["cot"])
+    plan.run(PHASE_BWD, dev)
+    torch.cuda.synchronize()
+    assert plan.status() == 0
+    res = {"y": plan.io(dev, "y", (lc.B, co, Fo, To)).cpu(), "dx": plan.io(dev, "grad_x", (lc.B, ci, F, T)).cpu()}
+    for key in ("y", "dx"):
+        got, want = res[key].to(torch.bfloat16), ref[key].to(torch.bfloat16)
+        assert torch.equal(got.float(), res[key])                    # (the fp32 I/O tensor holds the plan's bf16 values)
+        assert torch.equal(got.view(torch.int16), want.view(torch.int16)), (name, key, int((got != want).sum()), "elements differ from the reference")
+    grads = read_params(plan, dev, ARENA_GRAD)
+    assert set(ref) == {"y", "dx"} | {"d/" + n for n in grads}
+    for n, v in grads.items():
+        assert torch.equal(v, ref["d/" + n]), (name, n, int((v != ref["d/" + n]).sum()), "elements differ from the reference")
 
 
 def test_bf16_cbn_plan_op_by_op():

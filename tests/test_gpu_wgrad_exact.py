@@ -1,7 +1,9 @@
 """Every weight-gradient kernel against exact sums, at every row split (exact_data.py; the CPU side is test_wgrad_exact_cpu.py).
 
-The forward and input-gradient kernel families have files of their own that vary the grid and compare bit for bit (test_gpu_rungemm_persist.py,
-test_gpu_thin_mask.py, test_gpu_thin_stage.py); this is the weight gradients' one.  Knob WG_NSPLIT varies the row splits at a fixed shape:
+The other two kinds of launch, the forward and the input-gradient GEMMs (OP_RUNGEMM of both phases), are held to the same bar - byte equality with the
+simulator on integer data, on every kernel family at every grid - in test_gpu_rungemm_exact.py; test_gpu_rungemm_persist.py, test_gpu_thin_mask.py and
+test_gpu_thin_stage.py vary the grid on float data and compare the kernels with each other.  This is the weight gradients' file.  Knob WG_NSPLIT varies
+the row splits at a fixed shape:
 
   1       one workgroup per tile walks every row of every batch item (hundreds of ring steps, every batch boundary, every stage wrap);
   3       an uneven split with a batch boundary inside a split;

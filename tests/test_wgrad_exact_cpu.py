@@ -143,21 +143,7 @@ def _fed_by_fused(case):
 
 
 # ------------------------------------------------------------------------------------------------ planted faults
-def _operand(g, s, b, u, fo, j):
-    """(arena, element index) of run element (s, j) of row (b, u, fo), or None where the row reads a zero (hostsim.cpp a_elem)."""
-    sg = g.seg[s]
-    if sg.src < 0 or not 0 <= j < sg.len:
-        return None
-    tt, r = u + sg.dt, sg.off + fo * g.fstride[sg.src] + j
-    if not 0 <= tt < g.Tin[sg.src] or not 0 <= r < g.rowlen[sg.src]:
-        return None
-    return g.x[sg.src].arena, g.x[sg.src].off, b * g.bstride[sg.src] + tt * g.tstride[sg.src] + g.base[sg.src] + r
-
-
-def _typed(ar, arena, off, dt):
-    """The arena from byte `off` on as elements of dtype code `dt`."""
-    raw = ar[arena].view(torch.uint8)[off:]
-    return raw[:raw.numel() // 4 * 4].view(torch.bfloat16 if dt == 1 else torch.float32)
+_operand, _typed = ed.operand, ed.typed
 
 
 def _dy_row(g, ar, b, u, fo):
