@@ -210,10 +210,12 @@ enum RunFamily : int { kFamNone = 0, kFamEnc0 = 1, kFamCgemm256 = 2, kFamDirect 
 int rungemm_family(const RunGemm& d);
 // ... and the kernel launch_wgrad picks for a WGRAD descriptor (reported in the same bits): first layer on the spectrum, plain or with the BatchNorm backward
 // fused (enc0.hip); rank-N streaming kernel; LDS-DMA kernel as 256 x 256 tile, 256 x 256 with the bias from the ones MFMA, 128 x 512 tile, 128 / 64 / 32 wide
-// n tiles; register-staged bf16 kernel, 128 / 64 wide; fp32 kernel
+// n tiles; register-staged bf16 kernel, 128 / 64 wide; fp32 kernel; frame-staged kernel of the thin layers (thin_wgrad.hip)
 enum WgradFamily : int { kWgFamNone = 0, kWgFamEnc0 = 1, kWgFamEnc0Fused = 2, kWgFamRank = 3, kWgFamWide256 = 4, kWgFamWide256Ones = 5, kWgFamWide128 = 6,
-                         kWgFamDma128 = 7, kWgFamDma64 = 8, kWgFamDma32 = 9, kWgFamBf16_128 = 10, kWgFamBf16_64 = 11, kWgFamF32 = 12 };
+                         kWgFamDma128 = 7, kWgFamDma64 = 8, kWgFamDma32 = 9, kWgFamBf16_128 = 10, kWgFamBf16_64 = 11, kWgFamF32 = 12, kWgFamThin = 13 };
 int wgrad_family(const RunGemm& d);
+bool launch_thin_wgrad(const RunGemm& d, const ArenaBases& ab, hipStream_t st);      // frame-staged weight gradients of enc1, dec4 and the mask layer (thin_wgrad.hip)
+bool thin_wgrad_takes(const RunGemm& d);                                             // ... whether it takes `d` (launch_wgrad and wgrad_family both ask)
 void launch_misc(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st);
 void launch_istft_fft(const IstftFft& d, const ArenaBases& ab, hipStream_t st);

@@ -1343,6 +1343,7 @@ void launch_wgrad(const RunGemm& d0, const ArenaBases& ab, hipStream_t st) {
 #endif
   if (d.xdt == DT_BF16 && (d.flags & kRunAligned)) {
     if (d.flags & kRunWgWide) { if (d.Npad % 256 == 0) launch_wgrad_wide(d, ab, st); else launch_wgrad_wide128(d, ab, st); return; }
+    if (launch_thin_wgrad(d0, ab, st)) return;     // frame-staged kernel for the thin layers next to the mask layer (thin_wgrad.hip)
     switch (wgrad_tn(d.xdt, d.N, d.Npad)) {        // sefd_desc.h: the planner sized nsplit for the same tile
       case 128: launch_wgrad_dma<128>(d, ab, st); break;
       case 64: launch_wgrad_dma<64>(d, ab, st); break;
@@ -1371,6 +1372,7 @@ int wgrad_family(const RunGemm& d) {
   if ((d.flags & kRunRank) && wgrad_rank_form(d)) return kWgFamRank;
   if (d.xdt == DT_BF16 && (d.flags & kRunAligned)) {
     if (d.flags & kRunWgWide) return d.Npad % 256 != 0 ? kWgFamWide128 : (d.flags & kRunOnesMfma) ? kWgFamWide256Ones : kWgFamWide256;
+    if (thin_wgrad_takes(d)) return kWgFamThin;
     switch (wgrad_tn(d.xdt, d.N, d.Npad)) {
       case 128: return kWgFamDma128;
       case 64: return kWgFamDma64;

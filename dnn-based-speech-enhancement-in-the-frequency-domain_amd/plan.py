@@ -13,11 +13,18 @@ PHASE_FWD, PHASE_BWD = 0, 1
 RUN_FAMILY_NONE, RUN_FAMILY_ENC0, RUN_FAMILY_CGEMM256, RUN_FAMILY_DIRECT, RUN_FAMILY_TILED, RUN_FAMILY_PERSIST, RUN_FAMILY_THIN_MASK, RUN_FAMILY_THIN_STAGE = range(8)
 # ... of a WGRAD op (csrc/dev_common.h WgradFamily): the first layer on the spectrum, plain / with the BatchNorm backward fused; the rank-N streaming kernel;
 # the LDS-DMA kernel as 256 x 256 tile, 256 x 256 with the bias from the ones MFMA, 128 x 512 tile and 128 / 64 / 32 wide n tiles; the register-staged bf16
-# kernel (unaligned runs), 128 / 64 wide; the fp32 kernel
+# kernel (unaligned runs), 128 / 64 wide; the fp32 kernel; the frame-staged kernel of the thin layers (csrc/thin_wgrad.hip)
 (WG_FAMILY_NONE, WG_FAMILY_ENC0, WG_FAMILY_ENC0_FUSED, WG_FAMILY_RANK, WG_FAMILY_WIDE256, WG_FAMILY_WIDE256_ONES, WG_FAMILY_WIDE128,
- WG_FAMILY_DMA128, WG_FAMILY_DMA64, WG_FAMILY_DMA32, WG_FAMILY_BF16_128, WG_FAMILY_BF16_64, WG_FAMILY_F32) = range(13)
+ WG_FAMILY_DMA128, WG_FAMILY_DMA64, WG_FAMILY_DMA32, WG_FAMILY_BF16_128, WG_FAMILY_BF16_64, WG_FAMILY_F32, WG_FAMILY_THIN) = range(14)
 WG_FAMILY_NAMES = ("none", "first layer", "first layer fused", "rank-N", "256 x 256", "256 x 256 ones MFMA", "128 x 512", "aligned 128", "aligned 64",
                    "aligned 32", "unaligned bf16 128", "unaligned bf16 64", "fp32")
+# WG_FAMILY_NAMES stays the tuple of the families that every plan reaches by its shape alone (tests/test_wgrad_exact_cpu.py holds its cases to exactly that
+# list); a family taken only from a row threshold up, or under a knob, is named here.  wg_family_name() covers both
+WG_FAMILY_MORE_NAMES = {WG_FAMILY_THIN: "frame-staged thin"}
+
+
+def wg_family_name(family):
+    return WG_FAMILY_MORE_NAMES[family] if family in WG_FAMILY_MORE_NAMES else WG_FAMILY_NAMES[family]
 RUN_WAVE_ONLY = 1
 MASK_MODES = {"E": 0, "C": 1, "R": 2, "Direct(None make)": 4}
 DTYPES = {"fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
