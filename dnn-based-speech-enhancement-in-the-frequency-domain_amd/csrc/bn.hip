@@ -37,7 +37,8 @@ template <> struct VecIO<bf16_t> {
   }
 };
 
-constexpr int kMaxC = 1024;
+constexpr int kMaxC = kBnMaxC;                      // sefd_desc.h: the planner refuses a layer with more channels
+static_assert(kMaxC <= 1024, "bn_bwd_reduce_kernel_v: red[512 * V + 8] holds 256 V channels x 2 sums, and C / V chunk columns must fit 256 threads in fp32");
 
 // LDS parameter block: mean | invstd | gamma | beta  (each C floats)
 __device__ __forceinline__ void stage_params(float* sp, int C, const float* mi, const float* gamma, const float* beta) {

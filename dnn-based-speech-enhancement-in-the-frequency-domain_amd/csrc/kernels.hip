@@ -1,6 +1,6 @@
 // HBM-bound and recurrent kernels of the speech-enhancement hot path (gfx950).
 //   pack / splitsum / unpack   weight re-layout between the reference state_dict layout and the MFMA-friendly packing
-//   bn_*                       BatchNorm2d(train) + PReLU forward / backward on channels-last rows
+//   bn_*finalize*              BatchNorm2d(train) + PReLU: partial rows -> statistics / parameter gradients (the passes over the rows: bn.hip)
 //   lstm_fwd / lstm_bwd        persistent recurrence, W_hh resident in VGPRs as MFMA B-fragments, h exchanged through LDS
 //   combine, mask, ola, specout  complex-LSTM glue, cRM application (E/C/R), overlap-add + clamp, layout conversion
 #include <hip/hip_runtime.h>
@@ -169,110 +169,6 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const BnFinalize d, co
   }
 }
 
-__global__ __launch_bounds__(256) void bn_apply_kernel(const BnApply d, const ArenaBases ab) {
-  const char* y = rp(ab, d.y);
-  char* z = rp(ab, d.z);
-  const float* mi = reinterpret_cast<const float*>(rp(ab, d.mean_invstd));
-  const float* gamma = reinterpret_cast<const float*>(rp(ab, d.gamma));
-  const float* beta = reinterpret_cast<const float*>(rp(ab, d.beta));
-  const float a = *reinterpret_cast<const float*>(rp(ab, d.slope));
-  const int64_t n4 = d.R * d.C / 4;
-  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = q * 4;
-    const int c = (int)(i % d.C);
-    float4 v = ld4(y, d.dt, i);
-    float* pv = reinterpret_cast<float*>(&v);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float bn = gamma[c + e] * ((pv[e] - mi[c + e]) * mi[d.C + c + e]) + beta[c + e];
-      pv[e] = bn > 0.f ? bn : a * bn;
-    }
-    st4(z, d.dt, i, v);
-  }
-}
-
-// upstream gradient wrt z for y-row r, 4 channels starting at c
-__device__ __forceinline__ float4 load_dz(const BnBwdReduce& d, const char* dz0, const char* dz1, int64_t r, int c) {
-  float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int64_t b = r / d.rpb, q = r - b * d.rpb;
-  if (q >= d.skip) {
-    const int64_t dr = b * (d.rpb - d.skip) + q - d.skip;
-    g = ld4(dz0, d.dt, dr * d.C + c);
-  }
-  if (dz1) {
-    const float4 h = ld4(dz1, d.dt, r * d.C + c);
-    g.x += h.x; g.y += h.y; g.z += h.z; g.w += h.w;
-  }
-  return g;
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdReduce d, const ArenaBases ab) {
-  const char* y = rp(ab, d.y);
-  const char* dz0 = rp(ab, d.dz0);
-  const char* dz1 = d.dz1.arena >= 0 ? rp(ab, d.dz1) : nullptr;
-  const float* mi = reinterpret_cast<const float*>(rp(ab, d.mean_invstd));
-  const float* gamma = reinterpret_cast<const float*>(rp(ab, d.gamma));
-  const float* beta = reinterpret_cast<const float*>(rp(ab, d.beta));
-  const float a = *reinterpret_cast<const float*>(rp(ab, d.slope));
-  const int C4 = d.C / 4;
-  const int nrl = 256 / C4 > 0 ? 256 / C4 : 1;
-  __shared__ float red[2048 + 256];
-  float s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0}, sa = 0.f;
-  const int64_t row0 = (int64_t)blockIdx.x * d.rows_per_blk;
-  const int64_t row1 = min(d.R, row0 + d.rows_per_blk);
-  for (int cc0 = 0; cc0 < C4; cc0 += 256) {              // C4 <= 256 for every supported model; loop keeps it general
-    const int rl = C4 >= 256 ? 0 : threadIdx.x / C4;
-    const int cc = C4 >= 256 ? cc0 + threadIdx.x : threadIdx.x % C4;
-    if (cc < C4 && rl < nrl) {
-      const int c = cc * 4;
-      for (int64_t r = row0 + rl; r < row1; r += nrl) {
-        const float4 yv = ld4(y, d.dt, r * d.C + c);
-        const float4 gz = load_dz(d, dz0, dz1, r, c);
-        const float* py = reinterpret_cast<const float*>(&yv);
-        const float* pg = reinterpret_cast<const float*>(&gz);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float xh = (py[e] - mi[c + e]) * mi[d.C + c + e];
-          const float bn = gamma[c + e] * xh + beta[c + e];
-          const float dbn = bn > 0.f ? pg[e] : a * pg[e];
-          sa += bn > 0.f ? 0.f : bn * pg[e];
-          s0[e] += dbn;
-          s1[e] += dbn * xh;
-        }
-      }
-    }
-  }
-  // reduce over row-lanes (C4 < 256 case) through LDS: red[rl][C][2]
-  float* part = reinterpret_cast<float*>(rp(ab, d.part)) + (int64_t)blockIdx.x * 3 * d.C;
-  if (C4 < 256) {
-    const int rl = threadIdx.x / C4, cc = threadIdx.x % C4;
-    if (rl < nrl) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        red[(rl * d.C + cc * 4 + e) * 2 + 0] = s0[e];
-        red[(rl * d.C + cc * 4 + e) * 2 + 1] = s1[e];
-      }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < d.C; c += 256) {
-      float t0 = 0.f, t1 = 0.f;
-      for (int k = 0; k < nrl; ++k) { t0 += red[(k * d.C + c) * 2 + 0]; t1 += red[(k * d.C + c) * 2 + 1]; }
-      part[c] = t0;
-      part[d.C + c] = t1;
-    }
-  } else {
-    const int cc = threadIdx.x;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { part[cc * 4 + e] = s0[e]; part[d.C + cc * 4 + e] = s1[e]; }
-  }
-  __syncthreads();
-  sa = wave_sum(sa);
-  if ((threadIdx.x & 63) == 0) red[2048 + (threadIdx.x >> 6)] = sa;
-  __syncthreads();
-  if (threadIdx.x == 0) part[2 * d.C] = red[2048] + red[2049] + red[2050] + red[2051];
-  for (int c = 1 + threadIdx.x; c < d.C; c += blockDim.x) part[2 * d.C + c] = 0.f;     // row 2 holds per-channel shares (all in channel 0 here)
-}
-
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const BnBwdApply d, const ArenaBases ab) {
   const int c = blockIdx.x;
   const int C = d.r.C;
@@ -301,41 +197,6 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const BnBwdApply d
     reinterpret_cast<float*>(rp(ab, d.dbeta))[c] = (float)r0[0];
     reinterpret_cast<float*>(rp(ab, d.dgamma))[c] = (float)r1[0];
     if (c == 0) reinterpret_cast<float*>(rp(ab, d.dslope))[0] = (float)r2[0];
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdApply d, const ArenaBases ab) {
-  const BnBwdReduce& r = d.r;
-  const char* y = rp(ab, r.y);
-  const char* dz0 = rp(ab, r.dz0);
-  const char* dz1 = r.dz1.arena >= 0 ? rp(ab, r.dz1) : nullptr;
-  char* dy = rp(ab, d.dy);
-  const float* mi = reinterpret_cast<const float*>(rp(ab, r.mean_invstd));
-  const float* gamma = reinterpret_cast<const float*>(rp(ab, r.gamma));
-  const float* beta = reinterpret_cast<const float*>(rp(ab, r.beta));
-  const float* tot = reinterpret_cast<const float*>(rp(ab, d.totals));
-  const float a = *reinterpret_cast<const float*>(rp(ab, r.slope));
-  const float inv_n = (float)(1.0 / d.count);
-  const int C = r.C;
-  const int64_t n4 = r.R * C / 4;
-  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = q * 4;
-    const int64_t row = i / C;
-    const int c = (int)(i - row * C);
-    const float4 yv = ld4(y, r.dt, i);
-    const float4 gz = load_dz(r, dz0, dz1, row, c);
-    const float* py = reinterpret_cast<const float*>(&yv);
-    const float* pg = reinterpret_cast<const float*>(&gz);
-    float4 o;
-    float* po = reinterpret_cast<float*>(&o);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float xh = (py[e] - mi[c + e]) * mi[C + c + e];
-      const float bn = gamma[c + e] * xh + beta[c + e];
-      const float dbn = bn > 0.f ? pg[e] : a * pg[e];
-      po[e] = gamma[c + e] * mi[C + c + e] * (dbn - tot[c + e] * inv_n - xh * tot[C + c + e] * inv_n);
-    }
-    st4(dy, r.dt, i, o);
   }
 }
 

@@ -397,7 +397,15 @@ struct Builder {
 
   // BatchNorm2d + PReLU forward of a conv layer (parameters <pp>.1 / <pp>.2): y -> z.  Training: batch statistics from nblk partial rows
   // of pitch Cpad in `part` (nsub > 0: each row holds nsub sub-pixel phases substride columns apart)
+  // more than kBnMaxC channels: refused - bn.hip's LDS arrays hold no more (every launch of the layer would write past them)
+  bool bn_fits(const std::string& pp, int C) {
+    if (C <= kBnMaxC) return true;
+    if (P->error.empty())
+      P->error = "BatchNorm2d: at most " + std::to_string(kBnMaxC) + " channels per layer (bn.hip stages a layer's parameters in LDS): " + pp + " has " + std::to_string(C);
+    return false;
+  }
   void bn_fwd(std::vector<Op>& ops, int tag, const std::string& pp, const ConvLayer& Ly, Ptr part, int nblk, int Cpad, int nsub, int substride) {
+    if (!bn_fits(pp, Ly.C)) return;
     Op& op = push(ops, OP_BN_FINALIZE, tag);
     op.bnf.part = part; op.bnf.mean_invstd = Ly.mi;
     op.bnf.running_mean = sptr(pp + ".1.running_mean"); op.bnf.running_var = sptr(pp + ".1.running_var");
@@ -525,6 +533,7 @@ struct Builder {
       push(R, OP_CBN_BWD_APPLY, tag).cbb = cb;
       return a;
     }
+    if (!bn_fits(pp, C)) return a;
     BnBwdReduce r;
     std::memset(&r, 0, sizeof(r));
     r.y = y; r.dz0 = dz0; r.dz1 = dz1; r.mean_invstd = mi;

@@ -145,6 +145,9 @@ struct Unpack {
 };
 
 // BatchNorm2d (training) + PReLU on channels-last rows [R][C].
+// Most channels of one layer: bn.hip stages 4 * C floats of parameters in LDS and reduces a block of rows through an array sized for it; the
+// planner (plan_builder.h bn_fwd / bn_bwd) refuses a wider layer.
+constexpr int kBnMaxC = 1024;
 struct BnFinalize {            // partial sums -> mean, invstd ; running stats momentum update
   Ptr part;                    // [nblk][2][Cpad]
   Ptr mean_invstd;             // fp32 [2][C]  (workspace)

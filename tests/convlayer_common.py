@@ -41,6 +41,10 @@ CASES = {
 CBN_SHAPES = {"5x6": (5, 6), "33x5": (33, 5), "17": (17,)}
 CBN_MODES = {"train01": (True, 0.1), "train03": (True, 0.3), "eval": (False, 0.1)}
 CBN_CASES = {f"cbn{C}_{s}_{m}": (C, CBN_SHAPES[s], *CBN_MODES[m]) for C in (8, 24, 32, 40) for s in CBN_SHAPES for m in CBN_MODES}
+# ComplexBatchNorm on CORRELATED parts (C = 8, trailing shape (33, 5), training, momentum 0.1): imaginary = rho * real + sqrt(1 - rho^2) * noise.  The
+# covariance of a complex channel is then near singular (rho = 1: singular up to eps), where V^-1/2 and its derivative are ill-conditioned
+CORR_CASES = {"cbn8_corr09": 0.9, "cbn8_corr0999": 0.999, "cbn8_corr1": 1.0}
+CORR_C, CORR_REST, CORR_MOMENTUM = 8, (33, 5), 0.1
 STACK = "stack"                # the composition case: conv + ComplexBatchNorm + PReLU + transposed conv on [2, 2, 16, 9]
 STACK_SHAPE, STACK_OUT = (2, 2, 16, 9), (2, 2, 16, 10)      # 8 bins x 9 frames in between; the transposed conv adds a frame
 
@@ -124,6 +128,67 @@ def cbn_inputs(name, seed=SEED):
     shape = (B, C) + tuple(rest)
     x = _u(8002 + 16 * seed, shape) + 0.5 * _u(8003 + 16 * seed, (1, C) + (1,) * len(rest))      # per-channel offsets: means that matter
     return dict(x=x, cot=_u(8004 + 16 * seed, shape))
+
+
+def corr_inputs(name, seed=SEED):
+    rho, h = CORR_CASES[name], CORR_C // 2
+    shape = (B, h) + CORR_REST
+    real = _u(8009 + 16 * seed, shape).double() + 0.5 * _u(8010 + 16 * seed, (1, h, 1, 1)).double()
+    imag = rho * real + (1.0 - rho * rho) ** 0.5 * _u(8011 + 16 * seed, shape).double()
+    return dict(x=torch.cat([real, imag], 1).float(), cot=_u(8012 + 16 * seed, (B, CORR_C) + CORR_REST))
+
+
+# Per complex channel k (channels k and k + h of y / dx, element k of every parameter and buffer): the tensors of a ComplexBatchNorm result in
+# families that share one denominator - the channel's own largest reference value of the family
+CHANNEL_FAMILIES = {"y": ("y",), "dx": ("dx",), "dW": ("d/Wrr", "d/Wri", "d/Wii"), "dB": ("d/Br", "d/Bi"), "buf/RM": ("buf/RMr", "buf/RMi"),
+                    "buf/RV": ("buf/RVrr", "buf/RVri", "buf/RVii")}
+
+
+def channel_errors(got, ref):
+    """{family: float64 [h]}: max|got - ref| / max|ref| over the family's entries of complex channel k."""
+    out = {}
+    for fam, keys in CHANNEL_FAMILIES.items():
+        num, den = [], []
+        for key in keys:
+            g, r = torch.as_tensor(got[key]).double().cpu(), torch.as_tensor(ref[key]).double().cpu()
+            assert g.shape == r.shape, (key, g.shape, r.shape)
+            if r.dim() > 1:                                    # [B, 2h, ...] -> [h][everything of the channel]
+                h = r.shape[1] // 2
+                per = lambda t: torch.stack([t[:, :h], t[:, h:]], 0).transpose(0, 2).reshape(h, -1)
+            else:
+                per = lambda t: t.reshape(-1, 1)
+            num.append((per(g) - per(r)).abs().max(1).values)
+            den.append(per(r).abs().max(1).values)
+        den = torch.stack(den).max(0).values
+        out[fam] = torch.stack(num).max(0).values / torch.where(den > 0, den, torch.ones_like(den))
+    return out
+
+
+def load_corr_golden(name):
+    """(float64-reference tensors rounded to float32, {family: ref32 error [h]}, seed) of a correlated case."""
+    z = np.load(os.path.join(GOLDEN, f"convlayer_{name}.npz"))
+    ref = {k[4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("ref/")}
+    e32 = {k[len("ref32_err_ch/"):]: torch.from_numpy(z[k]).double() for k in z.files if k.startswith("ref32_err_ch/")}
+    return ref, e32, int(z["seed"])
+
+
+def check_per_channel(res, ref, e32, label="", report=None):
+    """check()'s rule per complex channel: every family's error of channel k within BAR * E32_k, E32_k = the largest error of the reference's own
+    float32 run among the families of channel k.  report: a file that receives both sides' figures."""
+    errs = channel_errors(res, ref)
+    E32 = torch.stack(list(e32.values())).max(0).values
+    lines = [f"{label}: per complex channel, this package's error | the reference's float32 error; bar {BAR} x the channel's largest float32 error"]
+    for fam in CHANNEL_FAMILIES:
+        lines.append(f"  {fam:7s} " + " ".join(f"{float(a):.2e}|{float(b):.2e}" for a, b in zip(errs[fam], e32[fam])))
+    lines.append("  E32     " + " ".join(f"{float(v):.2e}" for v in E32))
+    print("\n".join(lines))
+    if report is not None:
+        with open(report, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    for fam, e in errs.items():
+        for k in range(e.numel()):
+            assert float(e[k]) <= BAR * float(E32[k]), (label, fam, "complex channel", k, float(e[k]), BAR * float(E32[k]))
+    return errs
 
 
 def stack_inputs(seed=SEED):

@@ -1,7 +1,7 @@
 """Golden vectors for the conv layers and ComplexBatchNorm on their own (tools_for_model.py:199-607) and for one stack of them.
 
 RUN ONLY WHERE THE REFERENCE IS AVAILABLE (same import shim as make_golden.py, which is imported, never edited).  Per case of
-tests/convlayer_common (CASES, CBN_CASES, STACK; B = 2) the real reference modules run on the CPU in float64 (`module.double()`) and in float32:
+tests/convlayer_common (CASES, CBN_CASES, CORR_CASES, STACK; B = 2) the real reference modules run on the CPU in float64 (`module.double()`) and in float32:
 y = f(x), loss = sum(y * cot), backward.  Inputs, cotangents and parameter values are closed form (splitmix streams of oracle/weights.py at the
 stored seed: convlayer_common.fill_ / *_inputs), so a fixture holds the seed and the results only: every float64 output, input gradient,
 parameter gradient and buffer after the forward, rounded to float32, and per tensor ref32_err = max|ref32 - ref64| / max|ref64|.
@@ -40,6 +40,20 @@ def write(name, r64, r32):
     assert os.path.getsize(path) < MAX_BYTES, (path, os.path.getsize(path))
     print(f"convlayer_{name}: {os.path.getsize(path)} bytes, {sum(v.numel() for v in r64.values())} values, E32 {max(e32.values()):.2e}")
     return max(e32.values())
+
+
+def write_corr(name, r64, r32):
+    """A correlated ComplexBatchNorm case: the float64 results and, per complex channel and family of tensors, the float32 run's error."""
+    rec = dict(seed=lc.SEED)
+    for k, v in r64.items():
+        rec["ref/" + k] = v.float().numpy()
+    e32 = lc.channel_errors(r32, r64)
+    for fam, e in e32.items():
+        rec["ref32_err_ch/" + fam] = e.numpy()
+    path = os.path.join(HERE, f"convlayer_{name}.npz")
+    np.savez_compressed(path, **rec)
+    assert os.path.getsize(path) < MAX_BYTES, (path, os.path.getsize(path))
+    print(f"convlayer_{name}: {os.path.getsize(path)} bytes; float32 error per channel: " + ", ".join(f"{fam} {float(e.max()):.2e}" for fam, e in e32.items()))
 
 
 def both(build, inp, training=True, forward_of=None):
@@ -87,9 +101,13 @@ def main():
     for name, (C, rest, training, momentum) in lc.CBN_CASES.items():
         if not want or name in want:
             e.append(write(name, *both(lambda: tfm.ComplexBatchNorm(C, momentum=momentum), lc.cbn_inputs(name), training)))
+    for name in lc.CORR_CASES:
+        if not want or name in want:
+            write_corr(name, *both(lambda: tfm.ComplexBatchNorm(lc.CORR_C, momentum=lc.CORR_MOMENTUM), lc.corr_inputs(name), True))
     if not want or lc.STACK in want:
         e.append(write(lc.STACK, *both(lambda: lc.make_stack(tfm), lc.stack_inputs(), True, lc.stack_forward)))
-    print(f"E32 over {len(e)} cases: {min(e):.2e} .. {max(e):.2e}")
+    if e:
+        print(f"E32 over {len(e)} cases: {min(e):.2e} .. {max(e):.2e}")
 
 
 if __name__ == "__main__":

@@ -6,29 +6,11 @@ import ctypes as C
 import pytest
 import torch
 
+from norm_data import OP_HEADER, CbnBwd, CbnFwd, Ptr                 # the ctypes mirrors of sefd_desc.h, shared with the per-launch tier
 from simutil import PHASE_BWD, PHASE_FWD, Plan
 
 SMALL = dict(kernel_num=(16, 32, 32, 64, 64, 64), rnn_units=128)
 OP_CBN_FINALIZE, OP_CBN_BWD_FINALIZE = 43, 46          # sefd_desc.h OpKind (checked against the descriptors' own fields below)
-OP_HEADER = 16                                         # Op: kind, tag, lane, join, then the descriptor union
-
-
-class Ptr(C.Structure):
-    _fields_ = [("arena", C.c_int32), ("pad_", C.c_int32), ("off", C.c_int64)]
-
-
-class CbnFwd(C.Structure):                             # sefd_desc.h CbnFwd
-    _fields_ = [("y", Ptr), ("z", Ptr), ("part", Ptr), ("coef", Ptr), ("W", Ptr * 3), ("Bv", Ptr * 2), ("slope", Ptr), ("RM", Ptr * 2),
-                ("RV", Ptr * 3), ("R", C.c_int64), ("C", C.c_int32), ("dt", C.c_int32), ("nblk", C.c_int32), ("rows_per_blk", C.c_int32),
-                ("training", C.c_int32), ("mode", C.c_int32), ("count", C.c_double), ("eps", C.c_float), ("momentum", C.c_float),
-                ("totals", Ptr)]
-
-
-class CbnBwd(C.Structure):                             # sefd_desc.h CbnBwd
-    _fields_ = [("y", Ptr), ("dz0", Ptr), ("dz1", Ptr), ("dy", Ptr), ("coef", Ptr), ("coefb", Ptr), ("part", Ptr), ("W", Ptr * 3),
-                ("slope", Ptr), ("dW", Ptr * 3), ("dB", Ptr * 2), ("dslope", Ptr), ("R", C.c_int64), ("rpb", C.c_int64), ("C", C.c_int32),
-                ("dt", C.c_int32), ("nblk", C.c_int32), ("rows_per_blk", C.c_int32), ("skip", C.c_int32), ("mode", C.c_int32),
-                ("count", C.c_double), ("totals", Ptr)]
 
 
 def ops_bytes(plan, ph):

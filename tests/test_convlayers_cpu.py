@@ -269,3 +269,29 @@ def test_cbn_plans_and_host_simulator(name):
         err = lc.rel_err(res[key], v)
         print(f"{name} {key}: {err:.2e}")
         assert err < TOL, (name, key, err)
+
+
+@pytest.mark.parametrize("name", list(lc.CORR_CASES))
+def test_cbn_plan_on_correlated_parts_per_channel(name):
+    """ComplexBatchNorm where the imaginary part is rho * real + sqrt(1 - rho^2) * noise (rho 0.9, 0.999, 1: the covariance singular up to eps): the
+    fp32 plan on the host simulator against the reference's float64 run, per complex channel, at convlayer_common.BAR times the error of the
+    reference's own float32 run in that channel (convlayer_common.check_per_channel; the device's twin is in test_gpu_convlayers.py)."""
+    from sefd_amd import models
+    C, rest, S = lc.CORR_C, lc.CORR_REST, lc.CORR_REST[0] * lc.CORR_REST[1]
+    plan = Plan(lc.B, S, act_dtype="fp32", training=True, model="ComplexBatchNorm", cbn=dict(num_features=C, momentum=lc.CORR_MOMENTUM))
+    m = models.ComplexBatchNorm(C, momentum=lc.CORR_MOMENTUM)
+    lc.fill_(m, lc.SEED)
+    ref, e32, seed = lc.load_corr_golden(name)
+    inp = lc.corr_inputs(name, seed)
+    ar = plan.alloc_arenas("cpu")
+    fill_params(plan, ar, m.state_dict())
+    flat = lambda t: t.reshape(lc.B, C, 1, S)
+    _to_cl(plan, ar, "y", flat(inp["x"]), C)
+    _run_between_layout_ops(plan, PHASE_FWD, ar)
+    _to_cl(plan, ar, "dz", flat(inp["cot"]), C)
+    _run_between_layout_ops(plan, PHASE_BWD, ar)
+    shape = (lc.B, C) + tuple(rest)
+    res = {"y": act_to_nchw(plan.view(ar, "z"), lc.B, S, 1, C).reshape(shape), "dx": act_to_nchw(plan.view(ar, "dy"), lc.B, S, 1, C).reshape(shape)}
+    res.update({"d/" + n: v for n, v in read_params(plan, ar, ARENA_GRAD).items()})
+    res.update({"buf/" + n: v for n, v in read_params(plan, ar, ARENA_STATE, plan.state).items()})
+    lc.check_per_channel(res, ref, e32, name + " (host simulator)")

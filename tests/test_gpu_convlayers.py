@@ -66,6 +66,18 @@ def test_cbn_module_against_reference_golden(name):
         assert int(after["num_batches_tracked"]) == 0
 
 
+@pytest.mark.parametrize("name", list(lc.CORR_CASES))
+def test_cbn_module_on_correlated_parts_per_channel(name):
+    """Imaginary part = rho * real + sqrt(1 - rho^2) * noise (rho 0.9, 0.999, 1): every family of tensors of every complex channel within BAR times
+    the error of the reference's own float32 run in that channel; both sides' figures go to the report file."""
+    ref, e32, seed = lc.load_corr_golden(name)
+    m = _ns().ComplexBatchNorm(lc.CORR_C, momentum=lc.CORR_MOMENTUM)
+    res, m = _gpu(m, lc.corr_inputs(name, seed), True)
+    path = report_path(f"convlayers_{name}.txt")
+    open(path, "w").close()
+    lc.check_per_channel(res, ref, e32, name, report=path)
+
+
 def _layout(B, C, F, T, dt, mode, t_off, Tcl, nchw, cl):
     """One OP_NCHW_CL launch through the C ABI's test entry (sefd_nchw_cl): nchw / cl are device tensors."""
     import ctypes as ct

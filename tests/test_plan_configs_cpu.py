@@ -167,3 +167,24 @@ def test_table_reaches_every_descriptor_class():
         print(f"{name}: {seen.get(name)}")
     missing = [name for name in want if name not in seen]
     assert not missing, missing
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("model,kn5,channels", [("DCCRN", 1040, 1040), ("DCCRN", 2064, 2064), ("CRN", 2064, 1032), ("CRN", 4128, 2064)])
+def test_batchnorm_layer_wider_than_the_lds_staging_is_refused(model, kn5, channels, dtype):
+    """bn.hip stages 4 * C floats of a layer's parameters in LDS arrays sized for sefd_desc.h kBnMaxC = 1024 channels, and reduces a block of rows
+    through an array sized for it: a wider BatchNorm2d layer is refused by the conv stack both planners share, with the layer named - as the
+    ComplexBatchNorm branch refuses its own.  (The CRN's layers have kernel_num / 2 channels: its kernel_num[5] = 1040 is a 520-channel layer.)
+    Such a plan is never run: every BatchNorm launch of the layer would write past the arrays."""
+    kn = (16, 32, 32, 64, 64, kn5)
+    with pytest.raises(ValueError, match=rf"BatchNorm2d: at most 1024 channels per layer .*encoder\.5 has {channels}"):
+        Plan(1, 800, masking_mode="E", kernel_num=kn, rnn_units=128, act_dtype=dtype, model=model)
+    with pytest.raises(ValueError, match="BatchNorm2d: at most 1024 channels"):
+        Plan(1, 800, masking_mode="E", kernel_num=kn, rnn_units=128, act_dtype=dtype, model=model, training=False)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("model,kn5", [("DCCRN", 1024), ("CRN", 2048), ("CRN", 1040)])
+def test_batchnorm_layer_of_1024_channels_still_builds(model, kn5, dtype):
+    p = Plan(1, 800, masking_mode="E", kernel_num=(16, 32, 32, 64, 64, kn5), rnn_units=128, act_dtype=dtype, model=model)
+    assert p.params["encoder.5.1.weight"][1] == ((kn5 if model == "DCCRN" else kn5 // 2),)
