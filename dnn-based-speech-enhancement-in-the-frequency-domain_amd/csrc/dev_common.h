@@ -206,7 +206,9 @@ bool launch_thin_mask(const RunGemm& d, const ArenaBases& ab, hipStream_t st);  
 int thin_mask_grid(const RunGemm& d);                                                // ... its grid; 0: `d` stays where it was
 bool launch_thin_stage(const RunGemm& d, const ArenaBases& ab, hipStream_t st);      // frame-staged phase-merged thin layers: dec4 forward, enc1 input gradient (thin_stage.hip)
 int thin_stage_grid(const RunGemm& d);                                               // ... its grid; 0: `d` stays where it was
-enum RunFamily : int { kFamNone = 0, kFamEnc0 = 1, kFamCgemm256 = 2, kFamDirect = 3, kFamTiled = 4, kFamPersist = 5, kFamThinMask = 6, kFamThinStage = 7 };
+bool launch_thin_stage64(const RunGemm& d, const ArenaBases& ab, hipStream_t st);    // ... the strided form at 64 channels, 128 columns: enc2 forward, dec3 input gradients (thin_stage.hip)
+int thin_stage64_grid(const RunGemm& d);                                             // ... its grid; 0: `d` stays where it was (knobs of its own)
+enum RunFamily : int { kFamNone = 0, kFamEnc0 = 1, kFamCgemm256 = 2, kFamDirect = 3, kFamTiled = 4, kFamPersist = 5, kFamThinMask = 6, kFamThinStage = 7, kFamThinStage64 = 8 };
 int rungemm_family(const RunGemm& d);
 // ... and the kernel launch_wgrad picks for a WGRAD descriptor (reported in the same bits): first layer on the spectrum, plain or with the BatchNorm backward
 // fused (enc0.hip); rank-N streaming kernel; LDS-DMA kernel as 256 x 256 tile, 256 x 256 with the bias from the ones MFMA, 128 x 512 tile, 128 / 64 / 32 wide

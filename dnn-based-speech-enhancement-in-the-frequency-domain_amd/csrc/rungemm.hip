@@ -1290,6 +1290,7 @@ void launch_rungemm(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
   if (launch_cgemm256(d, ab, st)) return;                  // wide-tile kernel for the N >= 128 bf16 layers (cgemm256.hip)
   if (launch_thin_mask(d, ab, st)) return;                 // frame-staged kernels for the mask layer and its input gradient (thin_mask.hip)
   if (launch_thin_stage(d, ab, st)) return;                // ... for the phase-merged thin layers with statistics rows (thin_stage.hip)
+  if (launch_thin_stage64(d, ab, st)) return;              // ... for the 64-channel strided layers with 128 columns (thin_stage.hip)
   if (launch_rundirect(d, ab, st)) return;                 // direct-operand kernel for the thin bf16 layers (thin.hip)
   if (d.xdt == DT_BF16) launch_rungemm_t<bf16_t>(d, ab, st);
   else launch_rungemm_t<float>(d, ab, st);
@@ -1302,6 +1303,7 @@ int rungemm_family(const RunGemm& d) {
   if (d.flags & kRunWTile32) return kFamCgemm256;
   if (thin_mask_grid(d) > 0) return kFamThinMask;
   if (thin_stage_grid(d) > 0) return kFamThinStage;
+  if (thin_stage64_grid(d) > 0) return kFamThinStage64;
   if (rundirect_takes(d)) return kFamDirect;
   if (d.xdt == DT_BF16 && rungemm_persist_grid(d) > 0) return kFamPersist;
   return kFamTiled;

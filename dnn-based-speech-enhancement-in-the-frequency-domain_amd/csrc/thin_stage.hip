@@ -35,6 +35,7 @@ namespace sefd {
 namespace {
 
 constexpr int kStageFo = 64;                     // output positions per frame the kernel is built for
+constexpr int kStage64Fo = 32;                   // ... of the strided form at 64 channels (thin_stage64_grid)
 constexpr int64_t kThinStageMinRows = 262144;    // default rule: smaller launches stay on the kernels they had
 
 // every accumulator through ONE statement behind 16 wait states before the epilogue reads it in inline assembly (thin_mask.hip settle)
@@ -294,41 +295,53 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
 //     zero), so that the 16 output positions of a block read 16 CONSECUTIVE rows of one plane for every tap (a stride of two positions would use half
 //     the banks); chunk c of row r at c ^ swz(r);
 //   * wave w: column pair w % NCP, position group w / NCP: half a frame (two blocks of 16 positions), the whole frame at NCP = 4.  At NCP = 1 (the
-//     small plans' forward) the waves 2 and 3 only load.
+//     small plans' forward) the waves 2 and 3 only load;
+//   * FO, the output positions per frame, is a parameter of the geometry.  <64, 4, 32> is the next class up (profiles/thin_stage64_notes.md; selected by
+//     thin_stage64_grid under a knob of its own): 64 channels, 128 columns, K = 640 - the third encoder layer's forward conv and the two input gradients
+//     of the third-to-last decoder layer.  Four waves x 32 columns hold the 160 KB of weights in 160 registers each (two workgroups per CU); per wave and
+//     frame the MFMAs (80) and the fragment reads (40) are those of <32, 4, 64>.  A statistics row is four frames there.
 namespace {
 
-template <int C, int NCP>
+// FO: output positions per frame (2 FO input positions).  At C = 64, FO = 32 (the third encoder layer's forward conv, the third-to-last decoder layer's
+// input gradients: 128 columns, K = 640) a wave holds 160 registers of weights and a frame is ONE 32-row statistics group; the statistics then go
+// through an fp32 tile of the frame in LDS (TILE, see the kernel).
+template <int C, int NCP, int FO>
 struct StrideGeom {
   static constexpr int CPT = C / 8;              // 16-byte chunks per position
   static constexpr int PB = CPT * 16;            // bytes per position
-  static constexpr int PLANE = (kStageFo + 2) * PB;
+  static constexpr int PLANE = (FO + 2) * PB;
   static constexpr int SLOT = 2 * PLANE;
   static constexpr int KS = 2 * 5 * C / 32;      // K steps: 2 runs x 5 taps x C channels
-  static constexpr int NIT = 2 * kStageFo * CPT / 256;
+  static constexpr int NIT = 2 * FO * CPT / 256;
   static constexpr int RPL = 256 / PB;           // rows per bank line
-  static constexpr int NPH = NCP == 4 ? 1 : 2;   // position groups: waves that share a column pair, one 32-row statistics group each (a whole frame at NCP = 4)
-  static constexpr int NB = 4 / NPH;             // 16-position blocks per wave
+  static constexpr int FPR = 128 / FO;           // frames per statistics row
+  static constexpr int NPH = NCP == 4 ? 1 : 2;         // position groups: waves that share a column pair, one 32-row statistics group each (a whole frame at NPH = 1)
+  static constexpr int NB = FO / 16 / NPH;       // 16-position blocks per wave
   static constexpr int RED = NPH > 1 ? 2 * 4 * 2 * 8 * 16 : 0;   // statistics hand-over: [frame of the row][wave][sum, squares][q][h] x 16 bytes
-  static_assert((C == 32 || C == 16) && (NCP == 1 || NCP == 2 || NCP == 4) && NIT >= 1 && (2 * 5 * C) % 32 == 0, "instantiated forms");
+  static constexpr bool TILE = FO == 32;         // statistics chains walked by one lane per (column, chain) over the frame's fp32 tile in LDS
+  static constexpr int TP = 32 * NCP + 4;        // ... its pitch in floats: the two chains of a column start 4 rows apart, 16 banks apart
+  static constexpr int TILEB = TILE ? 32 * TP * 4 : 0;
+  static_assert((!TILE || FPR == 4) && ((FO == 64 && (C == 32 || C == 16) && (NCP == 1 || NCP == 2 || NCP == 4)) || (FO == 32 && C == 64 && NCP == 4)) && NIT >= 1 &&
+                (2 * 5 * C) % 32 == 0 && NB % 2 == 0 && (!TILE || (NPH == 1 && NB == 2)), "instantiated forms");
   __host__ __device__ static constexpr int swz(int row) { return (row / RPL) & (CPT - 1); }
 };
 
 }  // namespace
 
-template <int C, int NCP>
+template <int C, int NCP, int FO = kStageFo>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCP == 4 ? 2 : 3))) void thin_stage_st_kernel(const RunGemm d, const ArenaBases ab) {
-  using G = StrideGeom<C, NCP>;
-  constexpr int CPT = G::CPT, PB = G::PB, PLANE = G::PLANE, SLOT = G::SLOT, KS = G::KS, NIT = G::NIT, NB = G::NB;
-  __shared__ __attribute__((aligned(16))) char smem[3 * SLOT + G::RED];
+  using G = StrideGeom<C, NCP, FO>;
+  constexpr int CPT = G::CPT, PB = G::PB, PLANE = G::PLANE, SLOT = G::SLOT, KS = G::KS, NIT = G::NIT, NB = G::NB, FPR = G::FPR;
+  __shared__ __attribute__((aligned(16))) char smem[3 * SLOT + G::RED + G::TILEB];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, q = lane >> 4;
   const int cp = wid % NCP, ph = wid / NCP;      // this wave's column pair and position group
   const bool active = ph < G::NPH;               // (wave-uniform)
 
   const int Tout = d.Tout, Tin = d.Tin[0];
-  const int nframes = (int)(d.M / kStageFo), nrows = (nframes + 1) >> 1;
-  const int g0 = 2 * (int)((int64_t)blockIdx.x * nrows / gridDim.x);
-  int g1 = 2 * (int)((int64_t)(blockIdx.x + 1) * nrows / gridDim.x);
+  const int nframes = (int)(d.M / FO), nrows = (nframes + FPR - 1) / FPR;
+  const int g0 = FPR * (int)((int64_t)blockIdx.x * nrows / gridDim.x);
+  int g1 = FPR * (int)((int64_t)(blockIdx.x + 1) * nrows / gridDim.x);
   if (g1 > nframes) g1 = nframes;
   if (g0 >= g1) return;
 
@@ -377,10 +390,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCP == 4 ? 
   int eoff[NIT], edst[NIT];
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
-    const int L = it * 256 + tid, plane = L / (kStageFo * CPT), within = L % (kStageFo * CPT), row = 1 + within / CPT, c = (within % CPT) ^ G::swz(row);
+    const int L = it * 256 + tid, plane = L / (FO * CPT), within = L % (FO * CPT), row = 1 + within / CPT, c = (within % CPT) ^ G::swz(row);
     eoff[it] = (2 * (row - 1) + plane) * C + c * 8;
     const int L0 = it * 256 + wid * 64;
-    edst[it] = (L0 / (kStageFo * CPT)) * PLANE + PB + (L0 % (kStageFo * CPT)) * 16;
+    edst[it] = (L0 / (FO * CPT)) * PLANE + PB + (L0 % (FO * CPT)) * 16;
   }
   const uint32_t lbase = lds_addr(smem);
   const int64_t bs0 = d.bstride[0];
@@ -394,7 +407,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCP == 4 ? 
   // rows 0 and Fo + 1 of both planes of every slot: zero, never written again
   if (tid < 12 * CPT) {
     const int r = tid / CPT, slot = r / 4, plane = (r >> 1) & 1, last = r & 1;
-    *reinterpret_cast<uint4*>(smem + slot * SLOT + plane * PLANE + (last ? (kStageFo + 1) * PB : 0) + (tid % CPT) * 16) = make_uint4(0, 0, 0, 0);
+    *reinterpret_cast<uint4*>(smem + slot * SLOT + plane * PLANE + (last ? (FO + 1) * PB : 0) + (tid % CPT) * 16) = make_uint4(0, 0, 0, 0);
   }
 
   int cb = g0 / Tout, cu = g0 - cb * Tout;
@@ -443,7 +456,44 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCP == 4 ? 
       for (int blk = 0; blk < NB; ++blk) { acc[0][blk] += bias4[0]; acc[1][blk] += bias4[1]; }
       }
 
-      if (part) {
+      if constexpr (G::TILE) {
+        // One lane per (column, chain) over the frame's fp32 tile in LDS: 16 dependent add / fma steps where the DPP walk below takes 16 for each of a
+        // lane's 8 values.  The order is the 128-column kernels' (rungemm_persist_kernel<128>: two waves of 64 rows per column): chain hh of a column
+        // starts at 0.f and walks the rows 4 hh + 8 k + r of TWO consecutive frames without a restart; the pair is chain 0 + chain 1; the row is its two
+        // pairs added in ascending order to 0.f (a missing pair or frame of the launch's last row adds nothing, as rows beyond M add nothing there).
+        // The tile is written again behind the next frame's barrier, which the readers reach with their reads retired
+        if (part) {
+          float* tile = reinterpret_cast<float*>(smem + 3 * SLOT + G::RED);
+#pragma unroll
+          for (int blk = 0; blk < NB; ++blk)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) *reinterpret_cast<f32x4*>(tile + (16 * blk + li) * G::TP + 32 * cp + 8 * q + 4 * h) = acc[h][blk];
+          lds_barrier();
+          const int fr = (g - g0) % FPR, col = tid >> 1, hh = tid & 1;
+          if (fr == 0) { s1[0][0] = 0.f; s2[0][0] = 0.f; }
+          if ((fr & 1) == 0) { s1[0][1] = 0.f; s2[0][1] = 0.f; }
+          float s = s1[0][1], r = s2[0][1];      // this lane's chain over the pair of frames so far
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const float v = tile[(4 * hh + 8 * k + rr) * G::TP + col];
+              s = s + v;
+              r = __builtin_fmaf(v, v, r);
+            }
+          s1[0][1] = s; s2[0][1] = r;
+          const bool rowend = fr == FPR - 1 || left == 1;
+          if ((fr & 1) != 0 || rowend) {
+            s1[0][0] += s + dpp_f<0xB1>(s);      // quad_perm [1, 0, 3, 2]: the other chain of the column
+            s2[0][0] += r + dpp_f<0xB1>(r);
+          }
+          if (rowend && hh == 0) {
+            float* prow = part + (int64_t)(g / FPR) * 2 * d.Npad + col;
+            prow[0] = s1[0][0];
+            prow[d.Npad] = s2[0][0];
+          }
+        }
+      } else if (part) {
         // (order: see chain32.  A wave's pair of blocks is one 32-row group; the sums sit in lane li == 11)
         const int fr = (g - g0) & 1;
         const bool rowend = fr != 0 || left == 1;
@@ -516,11 +566,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCP == 4 ? 
 // ------------------------------------------------------------------------------------------------------------ selection
 namespace {
 
-// What both forms share: bf16 in and out, 16-byte aligned runs and output rows, a plain epilogue (bias, optional statistics), Fo = 64, whole frames.
-bool stage_common(const RunGemm& d) {
+// What all forms share: bf16 in and out, 16-byte aligned runs and output rows, a plain epilogue (bias, optional statistics), Fo = `fo`, whole frames.
+bool stage_common(const RunGemm& d, int fo = kStageFo) {
   if (d.xdt != DT_BF16 || d.ydt != DT_BF16 || !(d.flags & kRunAligned) || !(d.flags & kRunYAligned)) return false;
   if (d.flags & (kRunAccum | kRunRelu | kRunBnBwd | kRunWTile32 | kRunEnc0 | kRunDyFromBn | kRunRank)) return false;
-  if (d.zero.arena < 0 || d.M <= 0 || d.Tout <= 0 || d.Fo != kStageFo || (int64_t)d.M % ((int64_t)d.Tout * d.Fo) != 0 || d.x[0].arena < 0) return false;
+  if (d.zero.arena < 0 || d.M <= 0 || d.Tout <= 0 || d.Fo != fo || (int64_t)d.M % ((int64_t)d.Tout * d.Fo) != 0 || d.x[0].arena < 0) return false;
   if (d.y_fstride % 8 != 0 || d.y_off % 8 != 0 || d.y_tstride % 8 != 0 || d.y_bstride % 8 != 0 || d.ldw % 8 != 0) return false;
   if (d.n2 != 0 && (d.n2 < 0 || d.n2 % 8 != 0 || d.n2 >= d.N || d.y2.arena < 0)) return false;
   if (d.stats.arena >= 0 && (d.Npad != d.N || d.n2 != 0 || d.stats.off % 16 != 0)) return false;   // every column of a statistics row is written
@@ -571,6 +621,17 @@ int stage_form(const RunGemm& d) {
   return st ? st + 65536 : 0;
 }
 
+// The strided form at 64 channels and 32 output positions per frame, 128 columns (thin_stage_st_kernel<64, 4, 32>): the third encoder layer's forward
+// conv (bias, statistics rows) and the input gradients of the third-to-last decoder layer, one launch per destination (no statistics; a second
+// destination at n2 costs the kernel nothing and is allowed).  Field by field, as stage_st_form; no flag but the two alignment flags.
+bool stage64_form(const RunGemm& d) {
+  if (!stage_common(d, kStage64Fo) || (d.flags & ~(kRunAligned | kRunYAligned)) != 0 || d.x[1].arena >= 0) return false;
+  constexpr int C = 64;
+  if (d.fstride[0] != 2 * C || d.N != 128 || d.Npad != 128 || d.rowlen[0] != 2 * d.Fo * C) return false;
+  if (d.stats.arena < 0 && d.bias.arena >= 0) return false;      // the two epilogues built and measured: bias + statistics, or neither
+  return stage_runs(d, 1, -2 * C, 5 * C);
+}
+
 int stage_cus() {
   static const int ncu = [] {
     int dev = 0, n = 0;
@@ -607,7 +668,32 @@ int stage_resident(int form) {
   }
 }
 
+int stage64_resident() { static const int n = stage_wgs_per_cu(&thin_stage_st_kernel<64, 4, kStage64Fo>, 2); return n; }
+
 }  // namespace
+
+// Grid of the 64-channel strided launch of `d`, 0: the launch stays where it was.  Knobs of its own, read per launch: THIN_STAGE64 0 off, 1 the default
+// rule (launches of at least kThinStageMinRows rows), 2 every launch of the form; THIN_STAGE64_GRID 0 = resident workgroups, else a forced grid.  The unit
+// of a workgroup's run is a statistics row (four frames).  THIN_STAGE and THIN_MASK do not switch it.
+int thin_stage64_grid(const RunGemm& d) {
+  const int mode = (int)tune_int("THIN_STAGE64", 1);
+  if (mode <= 0 || !stage64_form(d)) return 0;
+  if (mode != 2 && d.M < kThinStageMinRows) return 0;
+  constexpr int fpr = 128 / kStage64Fo;
+  const int64_t units = (d.M / kStage64Fo + fpr - 1) / fpr;
+  int64_t grid = (int64_t)stage64_resident() * stage_cus();
+  const int64_t forced = tune_int("THIN_STAGE64_GRID", 0);
+  if (forced > 0) grid = forced;
+  if (grid > units) grid = units;
+  return (int)(grid < 1 ? 1 : grid);
+}
+
+bool launch_thin_stage64(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
+  const int grid = thin_stage64_grid(d);
+  if (grid <= 0) return false;
+  hipLaunchKernelGGL((thin_stage_st_kernel<64, 4, kStage64Fo>), dim3(grid), dim3(256), 0, st, d, ab);
+  return true;
+}
 
 // Grid of the frame-staged launch of `d`, 0: the launch stays where it was.  Knobs, read per launch: THIN_STAGE 0 off, 1 the default rule (launches of at
 // least kThinStageMinRows rows), 2 every launch of the form; THIN_STAGE_GRID 0 = resident workgroups, else a forced grid (the tests walk all frames

@@ -11,6 +11,10 @@ ARENA_WS, ARENA_PARAM, ARENA_GRAD, ARENA_STATE, ARENA_CONST, ARENA_IO, ARENA_COU
 PHASE_FWD, PHASE_BWD = 0, 1
 # op_info()["family"] of a RUNGEMM op (csrc/dev_common.h RunFamily)
 RUN_FAMILY_NONE, RUN_FAMILY_ENC0, RUN_FAMILY_CGEMM256, RUN_FAMILY_DIRECT, RUN_FAMILY_TILED, RUN_FAMILY_PERSIST, RUN_FAMILY_THIN_MASK, RUN_FAMILY_THIN_STAGE = range(8)
+# RUN_FAMILY_* stays the list of the families that tests/exact_data.py holds its cases to; a family taken only from a row threshold up, or under a knob of
+# its own, is named here: the strided frame-staged kernel at 64 channels and 128 columns (csrc/thin_stage.hip, knob THIN_STAGE64)
+RUNGEMM_FAMILY_THIN_STAGE64 = 8
+RUNGEMM_FAMILY_MORE_NAMES = {RUNGEMM_FAMILY_THIN_STAGE64: "frame-staged 64-channel strided"}
 # ... of a WGRAD op (csrc/dev_common.h WgradFamily): the first layer on the spectrum, plain / with the BatchNorm backward fused; the rank-N streaming kernel;
 # the LDS-DMA kernel as 256 x 256 tile, 256 x 256 with the bias from the ones MFMA, 128 x 512 tile and 128 / 64 / 32 wide n tiles; the register-staged bf16
 # kernel (unaligned runs), 128 / 64 wide; the fp32 kernel; the frame-staged kernel of the thin layers (csrc/thin_wgrad.hip)
