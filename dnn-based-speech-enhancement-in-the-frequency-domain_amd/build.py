@@ -10,13 +10,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsefd_hip.so")
-SOURCES = ["api.hip", "kernels.hip", "rungemm.hip", "rungemm_persist.hip", "cgemm256.hip", "enc0.hip", "lstm_bf16.hip", "lstm_cluster.hip", "lstm_rows.hip", "bn.hip", "cbn.hip", "lms.hip", "pmsqe.hip", "mix.hip", "composite.hip", "fsn.hip", "basemodel.hip", "stft_fft.hip", "thin.hip", "thin_mask.hip", "thin_stage.hip", "thin_wgrad.hip", "layout.hip", "optim.hip", "plan.cpp", "plan_dccrn.cpp", "plan_crn.cpp",
+SOURCES = ["api.hip", "kernels.hip", "rungemm.hip", "rungemm_persist.hip", "cgemm256.hip", "enc0.hip", "lstm_bf16.hip", "lstm_cluster.hip", "lstm_rows.hip", "bn.hip", "cbn.hip", "lms.hip", "pmsqe.hip", "mix.hip", "composite.hip", "stoi.hip", "fsn.hip", "basemodel.hip", "stft_fft.hip", "thin.hip", "thin_mask.hip", "thin_stage.hip", "thin_wgrad.hip", "layout.hip", "optim.hip", "plan.cpp", "plan_dccrn.cpp", "plan_crn.cpp",
            "plan_fsn.cpp", "plan_seq.cpp", "plan_clstm.cpp", "plan_frontend.cpp", "plan_layers.cpp", "tuning.cpp"]
 
 
 def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hs.append(os.path.join(HERE, "..", "include", "sefd.h"))
+    hs.append(os.path.join(HERE, "csrc_host", "stoi_tables.h"))      # shared with the host scorer (csrc/stoi.hip)
     return [h for h in hs if os.path.exists(h)]
 
 

@@ -73,6 +73,7 @@ optimizer = 'Adam'          # 'Adam' or 'AdamW' (decoupled weight decay): what t
 weight_decay = 0.0          # non-zero: on the weights only, through model.get_params(weight_decay) (models.py:289); biases stay without decay
 amsgrad = False
 max_grad_norm = None        # a number: global-norm gradient clipping inside the fused step (torch.nn.utils.clip_grad_norm_'s formula)
+gpu_stoi = False            # True: on a cuda DEVICE the validation loop's scorers="default" scores STOI on the GPU (tools_for_estimate.stoi_batch) under the host PESQ
 train_data_path = None      # [N, 2, L] .npy files of (noisy, clean) pairs; dataloader.py:63-71 has placeholder paths
 valid_data_path = None
 test_data_path = None

@@ -9,54 +9,22 @@
 #include <cstdint>
 #include <thread>
 #include <vector>
+#include "stoi_tables.h"
 
 namespace sefd_pesq { double pesq_wb_mos_lqo(const double* ref, const double* deg, long n, double in_scale); }
 
 namespace {
 
-constexpr int kFs = 10000, kFrame = 256, kNfft = 512, kBands = 15, kSeg = 30;
-constexpr double kMinFreq = 150.0, kBeta = -15.0, kDynRange = 40.0;
-constexpr double kPi = 3.14159265358979323846;
-const double kEps = 2.220446049250313e-16;
-
-double bessel_i0(double x) {                       // series of the modified Bessel function (np.kaiser uses i0)
-  double s = 1.0, t = 1.0;
-  const double q = x * x / 4.0;
-  for (int k = 1; k < 200; ++k) { t *= q / ((double)k * k); s += t; if (t < 1e-18 * s) break; }
-  return s;
-}
-
-// Octave-style `resample` low-pass (Kaiser-windowed sinc, 60 dB, 10 % roll-off), unit DC gain
-std::vector<double> resample_window(int p, int q) {
-  { int a = p, b = q; while (b) { const int t = a % b; a = b; b = t; } p /= a; q /= a; }
-  const double fc = 1.0 / (2.0 * std::max(p, q)), roll = fc / 10.0, rej = 60.0;
-  const int L = (int)std::ceil((rej - 8.0) / (28.714 * roll));
-  const double beta = 0.1102 * (rej - 8.7);
-  std::vector<double> h(2 * L + 1);
-  double sum = 0;
-  for (int i = 0; i <= 2 * L; ++i) {
-    const double t = i - L, a = 2.0 * fc * t;
-    const double sinc = a == 0.0 ? 1.0 : std::sin(kPi * a) / (kPi * a);
-    const double r = 2.0 * i / (2.0 * L) - 1.0;
-    h[i] = 2.0 * p * fc * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / bessel_i0(beta);
-    sum += h[i];
-  }
-  for (double& v : h) v /= sum;
-  return h;
-}
+using namespace sefd_stoi;                          // constants, resample_window, polyphase_geometry, hann_inner, thirdoct_bins
 
 // scipy.signal.resample_poly(x, up, down, window=h) with zero padding: polyphase evaluation of  upfirdn(h * up, x, up, down)
 std::vector<double> resample_poly(const std::vector<double>& x, int up, int down, const std::vector<double>& win) {
-  int a = up, b = down;
-  while (b) { const int t = a % b; a = b; b = t; }
-  up /= a; down /= a;
-  if (up == 1 && down == 1) return x;
   const int64_t n_in = (int64_t)x.size();
-  int64_t n_out = n_in * up;
-  n_out = n_out / down + (n_out % down ? 1 : 0);
-  const int half = ((int)win.size() - 1) / 2;
-  const int pre = down - half % down;
-  const int64_t pre_remove = (half + pre) / down;
+  const PolyphaseGeometry g = polyphase_geometry(n_in, up, down, (int)win.size());
+  if (g.up == 1 && g.down == 1) return x;
+  up = g.up; down = g.down;
+  const int64_t n_out = g.n_out, pre_remove = g.pre_remove;
+  const int pre = g.pre;
   std::vector<double> y((size_t)n_out);
   // full output sample m = sum_k hp[k] * xu[m*down - k], xu[j] = x[j / up] when up | j;  hp = [0]*pre ++ win*up
   for (int64_t o = 0; o < n_out; ++o) {
@@ -97,12 +65,6 @@ void fft(std::vector<std::complex<double>>& a) {            // in-place radix-2,
   }
 }
 
-std::vector<double> hann_inner(int n) {                     // np.hanning(n + 2)[1:-1]
-  std::vector<double> w(n);
-  for (int i = 0; i < n; ++i) w[i] = 0.5 - 0.5 * std::cos(2.0 * kPi * (i + 1) / (n + 1));
-  return w;
-}
-
 double stoi_one(const float* clean, const float* est, int n, int fs) {
   std::vector<double> x(clean, clean + n), y(est, est + n);
   if (fs != kFs) {
@@ -134,15 +96,7 @@ double stoi_one(const float* clean, const float* est, int n, int fs) {
   }
   // ---- one-third octave band envelopes of the 256 / 128 STFT
   int lo[kBands], hi[kBands];
-  for (int b = 0; b < kBands; ++b) {
-    const double fl = kMinFreq * std::pow(2.0, (2.0 * b - 1.0) / 6.0), fh = kMinFreq * std::pow(2.0, (2.0 * b + 1.0) / 6.0);
-    double bl = 1e300, bh = 1e300;
-    for (int k = 0; k <= kNfft / 2; ++k) {
-      const double f = (double)kFs * k / kNfft;
-      if ((f - fl) * (f - fl) < bl) { bl = (f - fl) * (f - fl); lo[b] = k; }
-      if ((f - fh) * (f - fh) < bh) { bh = (f - fh) * (f - fh); hi[b] = k; }
-    }
-  }
+  thirdoct_bins(lo, hi);
   std::vector<int> starts;
   for (int i = 0; i < (int)x.size() - kFrame; i += hop) starts.push_back(i);
   const int nf = (int)starts.size();

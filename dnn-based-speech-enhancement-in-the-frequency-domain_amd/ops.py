@@ -11,7 +11,8 @@ through ctypes (no dispatcher hop inside the fused train step); `tests/test_gpu_
     torch.ops.sefd.adam_step_(param, grad, m, v, step, ...)   torch.optim.Adam.step on flat fp32 buffers, in place
     torch.ops.sefd.mix_snr(speech, bank, start, snr_db, q)   generate_noisy_data.py:46-67 on the GPU
     torch.ops.sefd.composite_measures(clean, enh, fs)         composite.m frame analysis: [B, 3] fp64 (trimmed LLR, trimmed WSS, segSNR)
-    torch.ops.sefd.plan_run(handle, phase, arenas)            one phase (0 forward, 1 backward) of a planned model: sefd_plan_run
+    torch.ops.sefd.stoi(clean, enh, fs)                       STOI per utterance: [B] fp64 (tools_for_estimate.stoi_batch)
+    torch.ops.sefd.plan_run(handle, phase, arenas)           one phase (0 forward, 1 backward) of a planned model: sefd_plan_run
     torch.ops.sefd.basemodel_norm(x, kind, sample_len)        BaseModel's seven norms (tools_for_model.py:881-1104) by number, differentiable w.r.t. x
     torch.ops.sefd.unfold(x, n)                               BaseModel.unfold (tools_for_model.py:806-837), differentiable w.r.t. x
 """
@@ -261,6 +262,19 @@ def composite_measures(clean: torch.Tensor, enhanced: torch.Tensor, fs: int) -> 
 @composite_measures.register_fake
 def _(clean, enhanced, fs):
     return clean.new_empty((clean.shape[0], 3), dtype=torch.float64)
+
+
+@torch.library.custom_op("sefd::stoi", mutates_args=())
+def stoi(clean: torch.Tensor, enhanced: torch.Tensor, fs: int) -> torch.Tensor:
+    """STOI of a batch on the device (sefd_stoi_gpu, the arithmetic of tools_for_estimate.cal_stoi): clean / enhanced [B, L] at rate fs ->
+    fp64 [B]."""
+    from .tools_for_estimate import stoi_batch
+    return stoi_batch(clean, enhanced, fs)
+
+
+@stoi.register_fake
+def _(clean, enhanced, fs):
+    return clean.new_empty((clean.shape[0],), dtype=torch.float64)
 
 
 # ---------------------------------------------------------------------------------------------- planned models

@@ -7,7 +7,10 @@ P.862 MOS-LQO, csrc_host/pesq.cpp) take
 
 The composite measure (tools_for_estimate.py:24-45, composite.m): `composite(clean_path, enhanced_path)` and `pesq_mos(clean_path,
 enhanced_path)` keep the reference signatures; `composite_batch(clean, enhanced)` scores cuda `[B, L]` batches, the frame analysis (WSS, LLR,
-segSNR) in HIP (csrc/composite.hip, sefd_composite_frames) overlapped with the host PESQ."""
+segSNR) in HIP (csrc/composite.hip, sefd_composite_frames) overlapped with the host PESQ.
+
+`stoi_batch(clean, enhanced)` is cal_stoi's arithmetic on the device (csrc/stoi.hip, sefd_stoi_gpu): cuda `[B, L]` in, cuda fp64 `[B]` out on
+the current stream; `composite_batch(..., stoi=True)` and the validation loop with `scorers="gpu"` run it under the host PESQ."""
 import ctypes as C
 import os
 import subprocess
@@ -20,7 +23,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libsefd_scorers.so")
 SRC = os.path.join(HERE, "csrc_host", "scorers.cpp")
 SRCS = [SRC, os.path.join(HERE, "csrc_host", "pesq.cpp")]
-HDRS = [os.path.join(HERE, "csrc_host", "pesq_tables.h")]
+HDRS = [os.path.join(HERE, "csrc_host", "pesq_tables.h"), os.path.join(HERE, "csrc_host", "stoi_tables.h")]
 _lib = None
 
 
@@ -120,12 +123,39 @@ def composite_frames(clean, enhanced, fs=None):
     return out
 
 
-def composite_batch(clean, enhanced, fs=None, pesq=True, nthreads=0):
+def stoi_batch(clean, enhanced, fs=None):
+    """STOI on the GPU (sefd_stoi_gpu; the arithmetic of cal_stoi / csrc_host/scorers.cpp stoi_one in fp64): cuda [B, L] clean / enhanced at
+    rate fs (default cfg.fs) -> cuda fp64 [B], launched on the current stream; nothing waits for the result."""
+    import torch
+    from . import _lib
+    fs = int(cfg.fs if fs is None else fs)
+    if not (clean.is_cuda and enhanced.is_cuda):
+        raise RuntimeError("sefd stoi_batch runs on the MI355X only (cuda tensors); there is no CPU fallback (cal_stoi is the host scorer)")
+    if clean.dim() != 2 or clean.shape != enhanced.shape:
+        raise ValueError(f"stoi: clean and enhanced must both be [B, L], got {tuple(clean.shape)} and {tuple(enhanced.shape)}")
+    clean = clean.float().contiguous()
+    enhanced = enhanced.float().contiguous()
+    B, L = clean.shape
+    L_ = _lib.lib()
+    nbytes = L_.sefd_stoi_ws_bytes(B, L, fs)
+    if nbytes < 0:
+        raise ValueError(f"stoi: unsupported shape / rate (B={B}, L={L}, fs={fs}): code {nbytes} (include/sefd.h sefd_stoi_gpu)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=clean.device)
+    out = torch.empty(B, dtype=torch.float64, device=clean.device)
+    rc = L_.sefd_stoi_gpu(clean.data_ptr(), enhanced.data_ptr(), B, L, fs, ws.data_ptr(), out.data_ptr(),
+                          torch.cuda.current_stream(clean.device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f"sefd_stoi_gpu failed ({rc})")
+    return out
+
+
+def composite_batch(clean, enhanced, fs=None, pesq=True, nthreads=0, stoi=False):
     """CSIG / CBAK / COVL of a batch (tools_for_estimate.py:24-33 with composite.m): cuda [B, L] clean / enhanced -> dict of float64 numpy [B]
     arrays csig, cbak, covl, segsnr, llr, wss, pesq.  The frame kernels run on the current stream while the host scores PESQ (cal_pesq's
     threaded port) on a copy; then, in the reference's order, composite.m clamps 3.093 - 1.029 LLR - 0.009 WSS (CSIG), 1.634 - 0.007 WSS +
     0.063 segSNR (CBAK) and 1.594 - 0.512 LLR - 0.007 WSS (COVL) to [1, 5] and the wrapper adds 0.603 / 0.478 / 0.805 PESQ afterwards, so a
-    result can leave [1, 5].  pesq=False skips PESQ (any supported rate): csig / cbak / covl / pesq are then NaN."""
+    result can leave [1, 5].  pesq=False skips PESQ (any supported rate): csig / cbak / covl / pesq are then NaN.  stoi=True adds "stoi"
+    (stoi_batch, launched before the host PESQ starts; needs a rate sefd_stoi_gpu takes)."""
     fs = int(cfg.fs if fs is None else fs)
     if not (clean.is_cuda and enhanced.is_cuda):
         raise RuntimeError("sefd composite runs on the MI355X only (cuda tensors); there is no CPU fallback")
@@ -133,6 +163,7 @@ def composite_batch(clean, enhanced, fs=None, pesq=True, nthreads=0):
         raise ValueError(f"composite: the PESQ port is 16 kHz wide-band only (fs={fs}); use pesq=False for the frame measures alone")
     host = (clean.float().cpu().numpy(), enhanced.float().cpu().numpy()) if pesq else None      # copied BEFORE the launch: no wait on it
     frames = composite_frames(clean, enhanced, fs)
+    stoi_dev = stoi_batch(clean, enhanced, fs) if stoi else None
     B = clean.shape[0]
     p = _pesq(host[1], host[0], fs, nthreads) if pesq else np.full(B, np.nan)
     m = frames.cpu().numpy()
@@ -140,7 +171,10 @@ def composite_batch(clean, enhanced, fs=None, pesq=True, nthreads=0):
     csig = np.clip(3.093 - 1.029 * llr - 0.009 * wss, 1.0, 5.0) + 0.603 * p
     cbak = np.clip(1.634 - 0.007 * wss + 0.063 * seg, 1.0, 5.0) + 0.478 * p
     covl = np.clip(1.594 - 0.512 * llr - 0.007 * wss, 1.0, 5.0) + 0.805 * p
-    return {"csig": csig, "cbak": cbak, "covl": covl, "segsnr": seg, "llr": llr, "wss": wss, "pesq": p}
+    res = {"csig": csig, "cbak": cbak, "covl": covl, "segsnr": seg, "llr": llr, "wss": wss, "pesq": p}
+    if stoi:
+        res["stoi"] = stoi_dev.cpu().numpy()
+    return res
 
 
 def read_wav_pair(clean: str, enhanced: str):

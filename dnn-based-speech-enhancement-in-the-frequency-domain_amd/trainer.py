@@ -195,7 +195,18 @@ def _validate(model, validation_loader, writer, dir_to_save, epoch, DEVICE, batc
     last batch's first utterance every 10th epoch, means over the batches.  `batch_fn(inputs, targets)` returns
     (tuple of n_losses loss tensors, enhanced waveforms [B, L])."""
     import numpy as np
-    if scorers == "default":
+    stoi_batch = None
+    if scorers == "default" and cfg.gpu_stoi and torch.device(DEVICE).type == "cuda":
+        scorers = "gpu"
+    if scorers == "gpu":
+        # STOI on the device (tools_for_estimate.stoi_batch), enqueued before the host copies and read after the host PESQ returns
+        if torch.device(DEVICE).type != "cuda":
+            raise RuntimeError(f'scorers="gpu" scores STOI on the MI355X only (DEVICE={DEVICE}); there is no CPU fallback '
+                               '(scorers="default" is the host path)')
+        from . import tools_for_estimate as te
+        te.lib()
+        scorers, stoi_batch = (te.cal_pesq, te.cal_stoi), te.stoi_batch
+    elif scorers == "default":
         scorers = _default_scorers()
     sums = [torch.zeros((), device=DEVICE) for _ in range(n_losses)]
     avg_pesq = avg_stoi = 0.0
@@ -217,8 +228,10 @@ def _validate(model, validation_loader, writer, dir_to_save, epoch, DEVICE, batc
                     acc += l
                 last = (inputs, targets, outputs)
                 if scorers is not None:
+                    stoi_dev = stoi_batch(targets, outputs) if stoi_batch is not None else None
                     est, clean = outputs.cpu().numpy(), targets.cpu().numpy()
-                    pesq, stoi = np.asarray(scorers[0](est, clean)).reshape(-1), np.asarray(scorers[1](est, clean)).reshape(-1)
+                    pesq = np.asarray(scorers[0](est, clean)).reshape(-1)
+                    stoi = np.asarray(scorers[1](est, clean)).reshape(-1) if stoi_dev is None else stoi_dev.cpu().numpy()
                     for p, s in zip(pesq, stoi):
                         f_score.write("PESQ {:.6f} | STOI {:.6f}\n".format(p, s))
                     avg_pesq += float(pesq.sum()) / len(inputs)
@@ -241,6 +254,7 @@ def _validate(model, validation_loader, writer, dir_to_save, epoch, DEVICE, batc
 def model_validate(model, validation_loader, writer, dir_to_save, epoch, DEVICE, scorers="default"):
     """trainer.py:188-241 (T-F masking).  Returns (validation_loss, avg_pesq, avg_stoi).  `scorers = (cal_pesq, cal_stoi)`, each
     `f(estimated[B, L] ndarray, clean[B, L] ndarray) -> per-utterance scores`; "default" = the package's C++ scorers;
+    "gpu" = host PESQ with STOI on the GPU underneath (cuda DEVICE only; what "default" means when cfg.gpu_stoi is set);
     None: no scoring (both averages NaN, no score file)."""
     def batch(inputs, targets):
         _, _, outputs = model(inputs, targets)

@@ -1,4 +1,5 @@
-"""`tools_for_estimate` under the reference's top-level module name (see dropin/models.py): cal_pesq / cal_stoi / cal_snr, composite / pesq_mos."""
+"""`tools_for_estimate` under the reference's top-level module name (see dropin/models.py): cal_pesq / cal_stoi / cal_snr, composite / pesq_mos,
+and the batched GPU scorers composite_batch / stoi_batch."""
 import os
 import sys
 

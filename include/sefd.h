@@ -222,6 +222,21 @@ int32_t sefd_mix_snr(const float* speech, const float* noise, const int64_t* noi
 #define SEFD_COMPOSITE_MAX_FRAMES (1 << 24)
 int64_t sefd_composite_ws_bytes(int32_t B, int32_t L, int32_t fs);
 int32_t sefd_composite_frames(const float* clean, const float* enhanced, int32_t B, int32_t L, int32_t fs, void* ws, double* out, void* stream);
+/* ---- STOI on the device (Taal et al. 2011 with the conventions of pystoi 0.3.3; reference tools_for_estimate.py:90-96) ---------------------
+ * The host scorer sefd_stoi_batch (include/sefd_scorers.h) restated in HIP, extended = False: for a batch of clean / estimated pairs (fp32
+ * [B][L] device, rate fs) resample to 10 kHz (resample_poly, Kaiser-windowed sinc; skipped at fs == 10000), drop the 256-sample Hann frames
+ * (hop 128, frames start while i < n - 256) of the clean signal more than 40 dB below its loudest, overlap-add the K kept ones, take the
+ * 512-point STFT of the result, 15 one-third octave band envelopes from 150 Hz, and the clipped, normalised correlation over every 30-frame
+ * segment: out[b] (fp64 device [B]) is its mean, or 1e-5 where fewer than 30 frames are left.  fp64 after the load.  Bit-identical from run
+ * to run and independent of the rest of the batch; the whole call (one table copy, five launches) is enqueued on `stream`, the host never
+ * waits, allocates or frees; safe from several host threads.  ws: sefd_stoi_ws_bytes(B, L, fs) bytes of device memory.
+ * Returns 0, -1 bad arguments (NULL, B outside 1..65535, L < 1, fs < 1), -2 launch failure, -3 an utterance of more than
+ * SEFD_STOI_MAX_SAMPLES samples at fs or at 10 kHz (2^26: 23 minutes at 48 kHz), -4 a rate whose reduced ratio 10000 / fs has a factor above
+ * 1024 (8, 10, 11.025, 16, 22.05, 24, 32, 44.1, 48 and 96 kHz all pass).  sefd_stoi_ws_bytes is host arithmetic only and returns the same
+ * negative codes for the same arguments. */
+#define SEFD_STOI_MAX_SAMPLES (1 << 26)
+int64_t sefd_stoi_ws_bytes(int32_t B, int32_t L, int32_t fs);
+int32_t sefd_stoi_gpu(const float* clean, const float* est, int32_t B, int32_t L, int32_t fs, void* ws, double* out, void* stream);
 int32_t sefd_fsn_targets(const float* noisy_c64, const float* clean_c64, int64_t n, float* mag, float* phase, float* cirm, void* stream);
 /* Its backward, one pass over the interleaved complex inputs (fp32 device, n bins).  Cotangents g_mag, g_phase [n] and g_cirm [n][2], each NULL for
  * "no gradient"; d_noisy / d_clean [n][2] (NULL: not wanted) receive (dL/dre, dL/dim) of that argument and are written once, no accumulation.
