@@ -230,8 +230,19 @@ inline int reflect_idx(int f, int F) { return f < 0 ? -f : (f >= F ? 2 * (F - 1)
 inline float sb_raw(const Fsn& d, const float* mt, const float* fbo, int t, int b, int f, int k) {
   const int n = (d.NB - 1) / 2;
   if (k < d.NB) return mt[((int64_t)t * d.B + b) * d.F + reflect_idx(f - n + k, d.F)];
-  return fbo[((int64_t)t * d.B + b) * d.FP + f];
+  return fbo[((int64_t)t * d.B + b) * d.FP + reflect_idx(f - (fsn_nfb(d) >> 1) + (k - d.NB), d.F)];   // the full-band window (sefd_desc.h struct Fsn)
 }
+// output activation of a SequenceModel head (0 none, 1 ReLU, 2 Tanh, 3 ReLU6) and its derivative at the pre-activation x / from the output y
+inline float head_act(int act, float x) {
+  return act == 1 ? std::max(x, 0.f) : act == 2 ? (float)std::tanh((double)x) : act == 3 ? std::min(std::max(x, 0.f), 6.f) : x;
+}
+inline double head_act_grad(int act, double x, double g) {
+  if (act == 1) return x > 0 ? g : 0.0;
+  if (act == 2) { const double y = std::tanh(x); return g * (1 - y * y); }
+  if (act == 3) return (x > 0 && x < 6) ? g : 0.0;
+  return g;
+}
+
 void means(const Fsn& d, const AB& ab, double count) {
   const float* sums = (const float*)rp(ab, d.sums);
   float* mu = (float*)rp(ab, d.aux2);
@@ -374,7 +385,7 @@ bool run_fsn(const Op& op, const AB& ab) {
     case OP_FSN_SBSUM:
     case OP_FSN_SBBWD_SUM: {
       const Fsn& d = op.fsn;
-      const int W = d.NB + 1;
+      const int W = fsn_w(d), WP = fsn_wp(d);
       float* sums = (float*)rp(ab, d.sums);
       for (int b = 0; b < d.B; ++b)
         for (int f = 0; f < d.F; ++f) {
@@ -383,7 +394,7 @@ bool run_fsn(const Op& op, const AB& ab) {
             for (int k = 0; k < W; ++k) {
               if (op.kind == OP_FSN_SBSUM) s += sb_raw(d, (const float*)rp(ab, d.in), (const float*)rp(ab, d.aux), t, b, f, k);
               else {
-                const int64_t o = (((int64_t)t * d.B + b) * d.F + f) * W + k;
+                const int64_t o = (((int64_t)t * d.B + b) * d.F + f) * WP + k;
                 s += (double)((const float*)rp(ab, d.in))[o] * ld(rp(ab, d.aux), d.dt, o);
               }
             }
@@ -394,11 +405,12 @@ bool run_fsn(const Op& op, const AB& ab) {
     }
     case OP_FSN_SBBUILD: {
       const Fsn& d = op.fsn;
-      const int W = d.NB + 1;
+      const int W = fsn_w(d), WP = fsn_wp(d);                 // rows stored WP wide, pad columns zero
       const float* mu = (const float*)rp(ab, d.sums);
-      for (int64_t i = 0; i < (int64_t)d.TP * d.B * d.F * W; ++i) {
-        const int k = (int)(i % W); const int64_t r = i / W; const int f = (int)(r % d.F); const int64_t tb = r / d.F;
+      for (int64_t i = 0; i < (int64_t)d.TP * d.B * d.F * WP; ++i) {
+        const int k = (int)(i % WP); const int64_t r = i / WP; const int f = (int)(r % d.F); const int64_t tb = r / d.F;
         const int b = (int)(tb % d.B), t = (int)(tb / d.B);
+        if (k >= W) { st(rp(ab, d.out), d.dt, i, 0.f); continue; }
         st(rp(ab, d.out), d.dt, i, norm_apply(d, ab, sb_raw(d, (const float*)rp(ab, d.in), (const float*)rp(ab, d.aux), t, b, f, k), mu, b, r));
       }
       return true;
@@ -408,7 +420,7 @@ bool run_fsn(const Op& op, const AB& ab) {
       const float* mt = (const float*)rp(ab, d.in);
       const float* fbo = d.src ? (const float*)rp(ab, d.aux) : nullptr;
       float* stt = (float*)rp(ab, d.stat);
-      const int W = d.src ? d.NB + 1 : d.F, nf = d.src ? d.F : 1;
+      const int W = d.src ? fsn_w(d) : d.F, nf = d.src ? d.F : 1;
       auto val = [&](int t, int b, int f, int j) { return d.src ? sb_raw(d, mt, fbo, t, b, f, j) : mt[((int64_t)t * d.B + b) * d.F + j]; };
       for (int b = 0; b < d.B; ++b) {
         if (d.mode == 2) {
@@ -437,8 +449,8 @@ bool run_fsn(const Op& op, const AB& ab) {
       const float* dsb = (const float*)rp(ab, d.in);
       const float* fbo = (const float*)rp(ab, d.aux);
       const float* stt = (const float*)rp(ab, d.stat);
-      float* out = (float*)rp(ab, d.out);
-      const int W = d.NB + 1;
+      float* out = (float*)rp(ab, d.out);                     // [TP][B][F][NFB]: one value per full-band column
+      const int W = fsn_w(d), WP = fsn_wp(d), NFB = fsn_nfb(d);
       const int64_t rows = (int64_t)d.B * d.F;
       for (int b = 0; b < d.B; ++b) {
         if (d.mode == 2) {
@@ -447,16 +459,16 @@ bool run_fsn(const Op& op, const AB& ab) {
           for (int f = 0; f < d.F; ++f) {
             double s1 = 0, g1 = 0;
             for (int t = 0; t < d.TP; ++t) for (int k = 0; k < W; ++k) {
-              const int64_t o = (((int64_t)t * d.B + b) * d.F + f) * W + k;
+              const int64_t o = (((int64_t)t * d.B + b) * d.F + f) * WP + k;
               g1 += dsb[o]; s1 += (double)dsb[o] * ld(rp(ab, d.aux2), d.dt, o);
             }
             part[b * d.F + f] = (float)s1; part[(d.B + b) * d.F + f] = (float)g1;
             S += s1; G += g1;
           }
           const double N = (double)d.F * W * d.TP, sdv = stt[d.B + b], sden = sdv + 1e-5;
-          for (int t = 0; t < d.TP; ++t) for (int f = 0; f < d.F; ++f) {
-            const int64_t o = (((int64_t)t * d.B + b) * d.F + f) * W + d.NB;
-            out[((int64_t)t * d.B + b) * d.F + f] = (float)((dsb[o] - G / N) / sden - (double)ld(rp(ab, d.aux2), d.dt, o) * S / ((N - 1) * sdv));
+          for (int t = 0; t < d.TP; ++t) for (int f = 0; f < d.F; ++f) for (int j = 0; j < NFB; ++j) {
+            const int64_t o = (((int64_t)t * d.B + b) * d.F + f) * WP + d.NB + j;
+            out[(((int64_t)t * d.B + b) * d.F + f) * NFB + j] = (float)((dsb[o] - G / N) / sden - (double)ld(rp(ab, d.aux2), d.dt, o) * S / ((N - 1) * sdv));
           }
           continue;
         }
@@ -464,18 +476,21 @@ bool run_fsn(const Op& op, const AB& ab) {
           const int64_t row = (int64_t)b * d.F + f;
           double accA = 0, accB = 0, accBM = 0;
           for (int t = d.TP - 1; t >= 0; --t) {
-            const int64_t o = ((int64_t)t * rows + row) * W;
+            const int64_t o = ((int64_t)t * rows + row) * WP;
             double G = 0, S = 0;
             for (int k = 0; k < W; ++k) { G += dsb[o + k]; S += (double)dsb[o + k] * ld(rp(ab, d.aux2), d.dt, o + k); }
-            const double m = stt[((int64_t)t * rows + row) * 2], sd = stt[((int64_t)t * rows + row) * 2 + 1], n = (double)W * (t + 1), gk = dsb[o + d.NB];
-            double v;
-            if (d.mode == 1) { const double den = m + (double)kNormEps; accA += S / (den * n); v = gk / den - accA; }
+            const double m = stt[((int64_t)t * rows + row) * 2], sd = stt[((int64_t)t * rows + row) * 2 + 1], n = (double)W * (t + 1);
+            double den = sd;
+            if (d.mode == 1) { den = m + (double)kNormEps; accA += S / (den * n); }
             else {
               const double bb = S / (n * sd * sd);
               accA += G / (n * sd); accB += bb; accBM += bb * m;
-              v = gk / sd - accA - (double)fbo[((int64_t)t * d.B + b) * d.FP + f] * accB + accBM;
             }
-            out[((int64_t)t * d.B + b) * d.F + f] = (float)v;
+            for (int j = 0; j < NFB; ++j) {
+              double v = dsb[o + d.NB + j] / den - accA;
+              if (d.mode != 1) v = v - (double)fbo[((int64_t)t * d.B + b) * d.FP + reflect_idx(f - (NFB >> 1) + j, d.F)] * accB + accBM;
+              out[(((int64_t)t * d.B + b) * d.F + f) * NFB + j] = (float)v;
+            }
           }
         }
       }
@@ -485,18 +500,23 @@ bool run_fsn(const Op& op, const AB& ab) {
       const Fsn& d = op.fsn;
       const float* sbo = (const float*)rp(ab, d.in);
       float* crm = (float*)rp(ab, d.out);
+      const int act = fsn_sbact(d);
       for (int64_t i = 0; i < (int64_t)d.B * d.F * d.T * 2; ++i) {
         const int cch = (int)(i & 1); const int64_t q = i >> 1; const int t = (int)(q % d.T); const int64_t bf = q / d.T;
-        crm[i] = sbo[(((int64_t)(t + d.LA)) * d.B * d.F + bf) * 2 + cch];
+        crm[i] = head_act(act, sbo[(((int64_t)(t + d.LA)) * d.B * d.F + bf) * 2 + cch]);
       }
       return true;
     }
     case OP_FSN_OUT_BWD: {
       const Fsn& d = op.fsn;
       const float* g = (const float*)rp(ab, d.in);
+      const int act = fsn_sbact(d);
+      const float* pre = act ? (const float*)rp(ab, d.aux) : nullptr;      // the head's pre-activation, same layout as the output
       for (int64_t i = 0; i < (int64_t)d.TP * d.B * d.F * 2; ++i) {
         const int cch = (int)(i & 1); const int64_t q = i >> 1; const int64_t bf = q % ((int64_t)d.B * d.F); const int t = (int)(q / ((int64_t)d.B * d.F));
-        st(rp(ab, d.out), d.dt, i, t >= d.LA ? g[(bf * d.T + (t - d.LA)) * 2 + cch] : 0.f);
+        double v = t >= d.LA ? g[(bf * d.T + (t - d.LA)) * 2 + cch] : 0.0;
+        if (act && t >= d.LA) v = head_act_grad(act, pre[i], v);
+        st(rp(ab, d.out), d.dt, i, (float)v);
       }
       return true;
     }
@@ -567,26 +587,40 @@ bool run_fsn(const Op& op, const AB& ab) {
       const float* fbo = (const float*)rp(ab, d.aux);
       const float* mu = (const float*)rp(ab, d.aux2);
       const float* Sm = (const float*)rp(ab, d.sums);
-      const int W = d.NB + 1;
-      for (int64_t i = 0; i < (int64_t)d.TP * d.B * d.FP; ++i) {
-        const int f = (int)(i % d.FP); const int64_t tb = i / d.FP; const int b = (int)(tb % d.B);
-        float v = 0.f;
-        if (f < d.F) {
-          if (d.mode == 0) { const float den = mu[b] + 1e-5f; v = dsb[(tb * d.F + f) * W + d.NB] / den - Sm[b] / den; }
-          else v = dsb[tb * d.F + f];
-          const float y = fbo[i];
-          if (d.act == 1) v = y > 0.f ? v : 0.f; else if (d.act == 2) v *= (1.f - y * y); else if (d.act == 3) v = (y > 0.f && y < 6.f) ? v : 0.f;
+      const int WP = fsn_wp(d), NFB = fsn_nfb(d), nf = NFB >> 1;
+      // full-band bin g collects every column (f, j) of the window with reflect(f - nf + j) == g: the transpose of sb_raw's gather
+      const int ld_ = d.mode == 0 ? WP : NFB, c0 = d.mode == 0 ? d.NB : 0;
+      for (int64_t tb = 0; tb < (int64_t)d.TP * d.B; ++tb) {
+        const int b = (int)(tb % d.B);
+        std::vector<double> s(d.F, 0.0);
+        std::vector<int> cnt(d.F, 0);
+        for (int f = 0; f < d.F; ++f)
+          for (int j = 0; j < NFB; ++j) { const int g = reflect_idx(f - nf + j, d.F); s[g] += dsb[(tb * d.F + f) * ld_ + c0 + j]; ++cnt[g]; }
+        for (int f = 0; f < d.FP; ++f) {
+          float v = 0.f;
+          if (f < d.F) {
+            if (d.mode == 0) { const float den = mu[b] + 1e-5f; v = (float)s[f] / den - (float)cnt[f] * Sm[b] / den; }   // mean's term once per source
+            else v = (float)s[f];
+            const float y = fbo[tb * d.FP + f];
+            if (d.act == 1) v = y > 0.f ? v : 0.f; else if (d.act == 2) v *= (1.f - y * y); else if (d.act == 3) v = (y > 0.f && y < 6.f) ? v : 0.f;
+          }
+          st(rp(ab, d.out), d.dt, tb * d.FP + f, v);
         }
-        st(rp(ab, d.out), d.dt, i, v);
       }
+      return true;
+    }
+    case OP_FSN_ACT: {
+      const Fsn& d = op.fsn;
+      float* y = (float*)rp(ab, d.out);
+      for (int64_t i = 0; i < (int64_t)d.TP * d.B * d.FP; ++i) y[i] = head_act(d.act, y[i]);
       return true;
     }
     default: return false;
   }
 }
 
-void run_op(const Op& op, const AB& ab) {
-  if (run_fsn(op, ab)) return;
+bool run_op(const Op& op, const AB& ab) {                  // false: an op kind the simulator does not know
+  if (run_fsn(op, ab)) return true;
   switch (op.kind) {
     case OP_RUNGEMM: rungemm(op.g, ab); break;
     case OP_WGRAD: wgrad(op.g, ab); break;
@@ -1201,8 +1235,9 @@ void run_op(const Op& op, const AB& ab) {
       break;
     }
     case OP_MEMSET: std::memset(rp(ab, op.ms.dst), 0, op.ms.bytes); break;
-    default: std::fprintf(stderr, "hostsim: unknown op %d\n", op.kind);
+    default: std::fprintf(stderr, "hostsim: unknown op %d\n", op.kind); return false;
   }
+  return true;
 }
 }  // namespace
 
@@ -1216,7 +1251,7 @@ extern "C" int hostsim_run(const void* ops_, int first, int last, void* const* a
       std::fprintf(stderr, "hostsim: op %d (kind %d, tag %d) carries kRunEnc0 / kRunDyFromBn but fails enc0_accepts\n", i, ops[i].kind, ops[i].tag);
       return -1;
     }
-    run_op(ops[i], ab);
+    if (!run_op(ops[i], ab)) return -2;                       // nothing may be compared with a run that skipped an op
   }
   return 0;
 }
