@@ -27,6 +27,7 @@
 #include "sefd_desc.h"
 #include "tuning.h"
 #include "dev_common.h"
+#include "launch_common.h"
 
 namespace sefd {
 
@@ -472,13 +473,18 @@ __global__ __launch_bounds__(512) void cgemm256_kernel(const RunGemm d, const Ar
 int g_cgemm256_dbg = -1;       // tuning builds (-DSEFD_TUNING: tools/probes, A/B libraries) only: kernel variant set by a probe; -1 = the knob CG256_DBG, read per launch
 #endif
 
-// The planner decides which GEMMs take this kernel: it marks them (and packs their weights) with kRunWTile32.
-bool launch_cgemm256(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
+// The planner decides which GEMMs take this kernel: it marks them (and packs their weights) with kRunWTile32.  One workgroup per CU at the most;
+// form 1: the BatchNorm-backward epilogue.
+bool cgemm256_choose(const RunGemm& d, KernelChoice* c) {
   if (!(d.flags & kRunWTile32)) return false;
-  static const int ncu = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-  const int total = ((d.M + 255) / 256) * (d.Npad / 256);
-  const dim3 grid(total < ncu ? total : ncu);
-  const bool bnb = (d.flags & kRunBnBwd) != 0;
+  const int total = ((d.M + 255) / 256) * (d.Npad / 256), ncu = device_cus();
+  *c = KernelChoice{kFamCgemm256, (d.flags & kRunBnBwd) ? 1 : 0, total < ncu ? total : ncu};
+  return true;
+}
+
+void cgemm256_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st) {
+  const dim3 grid(c.grid);
+  const bool bnb = c.form != 0;
 #define SEFD_CG256_LAUNCH(DBG)                                                                                              \
   do {                                                                                                                      \
     if (bnb) hipLaunchKernelGGL((cgemm256_kernel<true, DBG>), grid, dim3(512), 0, st, d, ab);                               \
@@ -487,20 +493,19 @@ bool launch_cgemm256(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
 #ifdef SEFD_TUNING
   // wrong-result / experimental arms exist in tuning builds only: the product library has no switch that changes what a launch computes
   switch (g_cgemm256_dbg >= 0 ? g_cgemm256_dbg : (int)tune_int("CG256_DBG", 0)) {
-    case 1: SEFD_CG256_LAUNCH(1); return true;
-    case 2: SEFD_CG256_LAUNCH(2); return true;
-    case 4: SEFD_CG256_LAUNCH(4); return true;
-    case 8: SEFD_CG256_LAUNCH(8); return true;
-    case 32: SEFD_CG256_LAUNCH(32); return true;
-    case 64: SEFD_CG256_LAUNCH(64); return true;
-    case 128: SEFD_CG256_LAUNCH(128); return true;
-    case 256: SEFD_CG256_LAUNCH(256); return true;
+    case 1: SEFD_CG256_LAUNCH(1); return;
+    case 2: SEFD_CG256_LAUNCH(2); return;
+    case 4: SEFD_CG256_LAUNCH(4); return;
+    case 8: SEFD_CG256_LAUNCH(8); return;
+    case 32: SEFD_CG256_LAUNCH(32); return;
+    case 64: SEFD_CG256_LAUNCH(64); return;
+    case 128: SEFD_CG256_LAUNCH(128); return;
+    case 256: SEFD_CG256_LAUNCH(256); return;
     default: break;
   }
 #endif
   SEFD_CG256_LAUNCH(0);
 #undef SEFD_CG256_LAUNCH
-  return true;
 }
 
 }  // namespace sefd

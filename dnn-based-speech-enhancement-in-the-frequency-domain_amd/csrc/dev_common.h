@@ -192,22 +192,11 @@ struct StreamKey {
 struct StreamKeyHash { size_t operator()(const StreamKey& k) const { return (size_t)(uintptr_t)k.st * 31u + (size_t)k.dev; } };
 inline StreamKey stream_key(hipStream_t st) { int dev = 0; (void)hipGetDevice(&dev); return StreamKey{dev, st}; }
 
+// The conv GEMM launches (rungemm.hip): choose_rungemm / choose_wgrad ask the families below in a fixed order, written there alone; the launch hands the
+// choice to the family's launcher and rungemm_family / wgrad_family report its family.  The tiled, rank, wide, dma, bf16 and fp32 kernels are rungemm.hip's own.
 void launch_rungemm(const RunGemm& d, const ArenaBases& ab, hipStream_t st);
 void launch_wgrad(const RunGemm& d, const ArenaBases& ab, hipStream_t st);
-bool launch_cgemm256(const RunGemm& d, const ArenaBases& ab, hipStream_t st);
-bool launch_enc0_fwd(const RunGemm& d, const ArenaBases& ab, hipStream_t st);        // first encoder layer on the fp32 spectrum (enc0.hip)
-bool launch_enc0_wgrad(const RunGemm& d, const ArenaBases& ab, hipStream_t st);
-bool launch_rundirect(const RunGemm& d, const ArenaBases& ab, hipStream_t st);       // thin layers, N <= 64 (thin.hip)
-bool rundirect_takes(const RunGemm& d);                                              // ... whether it takes `d`
-bool launch_rungemm_persist(const RunGemm& d, const ArenaBases& ab, hipStream_t st); // persistent form of the 128-row LDS-DMA kernel (rungemm_persist.hip)
-int rungemm_persist_grid(const RunGemm& d);                                          // ... its grid; 0: `d` stays on rungemm_kernel
 // The kernel family launch_rungemm picks for a RUNGEMM descriptor under the knobs of the moment (sefd_plan_op_info reports it)
-bool launch_thin_mask(const RunGemm& d, const ArenaBases& ab, hipStream_t st);       // frame-staged mask-layer conv and its input gradient (thin_mask.hip)
-int thin_mask_grid(const RunGemm& d);                                                // ... its grid; 0: `d` stays where it was
-bool launch_thin_stage(const RunGemm& d, const ArenaBases& ab, hipStream_t st);      // frame-staged phase-merged thin layers: dec4 forward, enc1 input gradient (thin_stage.hip)
-int thin_stage_grid(const RunGemm& d);                                               // ... its grid; 0: `d` stays where it was
-bool launch_thin_stage64(const RunGemm& d, const ArenaBases& ab, hipStream_t st);    // ... the strided form at 64 channels, 128 columns: enc2 forward, dec3 input gradients (thin_stage.hip)
-int thin_stage64_grid(const RunGemm& d);                                             // ... its grid; 0: `d` stays where it was (knobs of its own)
 enum RunFamily : int { kFamNone = 0, kFamEnc0 = 1, kFamCgemm256 = 2, kFamDirect = 3, kFamTiled = 4, kFamPersist = 5, kFamThinMask = 6, kFamThinStage = 7, kFamThinStage64 = 8 };
 int rungemm_family(const RunGemm& d);
 // ... and the kernel launch_wgrad picks for a WGRAD descriptor (reported in the same bits): first layer on the spectrum, plain or with the BatchNorm backward
@@ -216,8 +205,28 @@ int rungemm_family(const RunGemm& d);
 enum WgradFamily : int { kWgFamNone = 0, kWgFamEnc0 = 1, kWgFamEnc0Fused = 2, kWgFamRank = 3, kWgFamWide256 = 4, kWgFamWide256Ones = 5, kWgFamWide128 = 6,
                          kWgFamDma128 = 7, kWgFamDma64 = 8, kWgFamDma32 = 9, kWgFamBf16_128 = 10, kWgFamBf16_64 = 11, kWgFamF32 = 12, kWgFamThin = 13 };
 int wgrad_family(const RunGemm& d);
-bool launch_thin_wgrad(const RunGemm& d, const ArenaBases& ab, hipStream_t st);      // frame-staged weight gradients of enc1, dec4 and the mask layer (thin_wgrad.hip)
-bool thin_wgrad_takes(const RunGemm& d);                                             // ... whether it takes `d` (launch_wgrad and wgrad_family both ask)
+// What a family's `choose` answers for a descriptor it takes (false: it declines, *c untouched) and its `launch` runs without asking again.
+// family: RunFamily / WgradFamily; form: the family's own index of the instantiation; grid: workgroups, 0 where the launcher derives it
+struct KernelChoice { int family; int form; int grid; };
+bool enc0_fwd_choose(const RunGemm& d, KernelChoice* c);              // first encoder layer of the bf16 plans on the fp32 spectrum (enc0.hip)
+void enc0_fwd_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st);
+bool enc0_wgrad_choose(const RunGemm& d, KernelChoice* c);            // ... and its weight gradient
+void enc0_wgrad_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st);
+bool cgemm256_choose(const RunGemm& d, KernelChoice* c);              // wide-tile kernel for the N >= 128 bf16 layers (cgemm256.hip)
+void cgemm256_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st);
+bool thin_mask_choose(const RunGemm& d, KernelChoice* c);             // frame-staged mask-layer conv and its input gradient (thin_mask.hip)
+void thin_mask_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st);
+// frame-staged thin layers: dec4 forward, enc1 input gradient, enc1 forward, dec4 input gradient (thin_stage.hip); and the strided form at
+// 64 channels, 128 columns: enc2 forward, dec3 input gradients - a family and knobs of its own, one launcher for both
+bool thin_stage_choose(const RunGemm& d, KernelChoice* c);
+bool thin_stage64_choose(const RunGemm& d, KernelChoice* c);
+void thin_stage_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st);
+bool rundirect_choose(const RunGemm& d, KernelChoice* c);             // direct-operand kernel for the thin layers, N <= 64 (thin.hip)
+void rundirect_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st);
+bool rungemm_persist_choose(const RunGemm& d, KernelChoice* c);       // persistent form of the 128-row LDS-DMA kernel (rungemm_persist.hip)
+void rungemm_persist_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st);
+bool thin_wgrad_choose(const RunGemm& d, KernelChoice* c);            // frame-staged weight gradients of enc1, dec4 and the mask layer (thin_wgrad.hip)
+void thin_wgrad_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st);
 void launch_misc(const Op& op, const ArenaBases& ab, hipStream_t st);
 void launch_stft_fft(const StftFft& d, const ArenaBases& ab, hipStream_t st);
 void launch_istft_fft(const IstftFft& d, const ArenaBases& ab, hipStream_t st);

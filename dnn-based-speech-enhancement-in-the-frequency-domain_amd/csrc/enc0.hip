@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "sefd_desc.h"
 #include "dev_common.h"
+#include "launch_common.h"
 
 namespace sefd {
 
@@ -278,30 +279,32 @@ __global__ __launch_bounds__(256) void enc0_wgrad_kernel(const RunGemm d, const 
   }
 }
 
-bool launch_enc0_fwd(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  if (!(d.flags & kRunEnc0) || !enc0_accepts(d, false)) return false;          // (sefd_desc.h)
+// Both launches: what sefd_desc.h enc0_accepts admits; the instantiations by output channels (16, 32, 64)
+static constexpr GemmKernel kEnc0Fwd[] = {&enc0_fwd_kernel<16>, &enc0_fwd_kernel<32>, &enc0_fwd_kernel<64>};
+static constexpr GemmKernel kEnc0Wgrad[] = {&enc0_wgrad_kernel<16, true>, &enc0_wgrad_kernel<16, false>, &enc0_wgrad_kernel<32, true>,
+                                            &enc0_wgrad_kernel<32, false>, &enc0_wgrad_kernel<64, true>, &enc0_wgrad_kernel<64, false>};      // ... x (BatchNorm backward fused, plain)
+static int enc0_width(const RunGemm& d) { return d.N <= 16 ? 0 : d.N <= 32 ? 1 : 2; }
+
+bool enc0_fwd_choose(const RunGemm& d, KernelChoice* c) {
+  if (!(d.flags & kRunEnc0) || !enc0_accepts(d, false)) return false;
   const int B = d.M / (d.Tout * d.Fo);
-  const dim3 grid((unsigned)(B * ((d.Tout + kE0Frames - 1) / kE0Frames)));
-  if (d.N <= 16) hipLaunchKernelGGL(enc0_fwd_kernel<16>, grid, dim3(256), 0, st, d, ab);
-  else if (d.N <= 32) hipLaunchKernelGGL(enc0_fwd_kernel<32>, grid, dim3(256), 0, st, d, ab);
-  else hipLaunchKernelGGL(enc0_fwd_kernel<64>, grid, dim3(256), 0, st, d, ab);
+  *c = KernelChoice{kFamEnc0, enc0_width(d), B * ((d.Tout + kE0Frames - 1) / kE0Frames)};
   return true;
 }
 
-bool launch_enc0_wgrad(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
+void enc0_fwd_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st) {
+  hipLaunchKernelGGL(kEnc0Fwd[c.form], dim3((unsigned)c.grid), dim3(256), 0, st, d, ab);
+}
+
+bool enc0_wgrad_choose(const RunGemm& d, KernelChoice* c) {
   if (!(d.flags & kRunEnc0) || !enc0_accepts(d, true)) return false;
-  const dim3 grid((unsigned)d.nsplit);
   const bool fuse = (d.flags & kRunDyFromBn) != 0;
-#define SEFD_E0W(CO)                                                                                              \
-  do {                                                                                                            \
-    if (fuse) hipLaunchKernelGGL((enc0_wgrad_kernel<CO, true>), grid, dim3(256), 0, st, d, ab);                   \
-    else hipLaunchKernelGGL((enc0_wgrad_kernel<CO, false>), grid, dim3(256), 0, st, d, ab);                       \
-  } while (0)
-  if (d.N <= 16) SEFD_E0W(16);
-  else if (d.N <= 32) SEFD_E0W(32);
-  else SEFD_E0W(64);
-#undef SEFD_E0W
+  *c = KernelChoice{fuse ? kWgFamEnc0Fused : kWgFamEnc0, 2 * enc0_width(d) + (fuse ? 0 : 1), d.nsplit};
   return true;
+}
+
+void enc0_wgrad_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st) {
+  hipLaunchKernelGGL(kEnc0Wgrad[c.form], dim3((unsigned)c.grid), dim3(256), 0, st, d, ab);
 }
 
 }  // namespace sefd

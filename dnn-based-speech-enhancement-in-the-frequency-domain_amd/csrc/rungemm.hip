@@ -1228,12 +1228,10 @@ __global__ __launch_bounds__(256) void wgrad_rank_kernel(const RunGemm d, const 
   }
 }
 
-static bool launch_wgrad_rank(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  if (!(d.flags & kRunRank) || !wgrad_rank_form(d)) return false;
+static void launch_wgrad_rank(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
   const dim3 grid((unsigned)d.nsplit);
   if (d.N <= 2) hipLaunchKernelGGL((wgrad_rank_kernel<2>), grid, dim3(256), 0, st, d, ab);
   else hipLaunchKernelGGL((wgrad_rank_kernel<4>), grid, dim3(256), 0, st, d, ab);
-  return true;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1243,7 +1241,7 @@ static bool launch_wgrad_rank(const RunGemm& d, const ArenaBases& ab, hipStream_
 // workgroups with a 2-stage ring, so that is the only configuration launched (and the only one built).
 // Those variants all held ONE lock-step workgroup per CU.  The same tile as a persistent kernel that keeps the co-residency (two workgroups of
 // 66 KB per CU at BN = 128, three at BN = 64 / 32), starts the next tile's first ring stage before the epilogue and keeps the epilogue in
-// registers is rungemm_persist.hip; launch_rungemm_t hands it the launches it takes (knob RG_PERSIST; profiles/rungemm_persist_notes.md).
+// registers is rungemm_persist.hip; choose_rungemm asks it in front of these kernels (knob RG_PERSIST; profiles/rungemm_persist_notes.md).
 template <typename TA, int BN>
 static void launch_rungemm_dma(const RunGemm& d, const ArenaBases& ab, hipStream_t st, int grid) {
   if (d.flags & kRunBnBwd) { hipLaunchKernelGGL((rungemm_kernel<TA, BN, true, 2, kBM, 4, false, true>), dim3(grid), dim3(256), 0, st, d, ab); return; }
@@ -1255,9 +1253,6 @@ static void launch_rungemm_t(const RunGemm& d, const ArenaBases& ab, hipStream_t
   const int bn = bn_of(d.N);
   const int nm = (d.M + kBM - 1) / kBM;
   const int grid = nm * (d.Npad / bn);
-  if constexpr (sizeof(TA) == 2) {
-    if (launch_rungemm_persist(d, ab, st)) return;         // bf16, aligned in and out, plain epilogue, enough tiles (rungemm_persist.hip)
-  }
   if (d.flags & kRunAligned) {
     if (bn == 128) launch_rungemm_dma<TA, 128>(d, ab, st, grid);
     else if (bn == 64) launch_rungemm_dma<TA, 64>(d, ab, st, grid);
@@ -1284,30 +1279,38 @@ static void refuse_launch(const ArenaBases& ab, hipStream_t st) {
   hipLaunchKernelGGL(refuse_launch_kernel, dim3(1), dim3(1), 0, st, ab.status, ab.dstatus);
 }
 
-void launch_rungemm(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  if (launch_enc0_fwd(d, ab, st)) return;                  // first encoder layer of the bf16 plans, on the fp32 spectrum (enc0.hip)
-  if (d.flags & (kRunEnc0 | kRunDyFromBn)) { refuse_launch(ab, st); return; }
-  if (launch_cgemm256(d, ab, st)) return;                  // wide-tile kernel for the N >= 128 bf16 layers (cgemm256.hip)
-  if (launch_thin_mask(d, ab, st)) return;                 // frame-staged kernels for the mask layer and its input gradient (thin_mask.hip)
-  if (launch_thin_stage(d, ab, st)) return;                // ... for the phase-merged thin layers with statistics rows (thin_stage.hip)
-  if (launch_thin_stage64(d, ab, st)) return;              // ... for the 64-channel strided layers with 128 columns (thin_stage.hip)
-  if (launch_rundirect(d, ab, st)) return;                 // direct-operand kernel for the thin bf16 layers (thin.hip)
-  if (d.xdt == DT_BF16) launch_rungemm_t<bf16_t>(d, ab, st);
-  else launch_rungemm_t<float>(d, ab, st);
+// THE order in which the RUNGEMM families are asked.  kFamNone: refused.  The tiled kernels take what nobody else does and derive tile and grid
+// from the descriptor (launch_rungemm_t).
+static KernelChoice choose_rungemm(const RunGemm& d) {
+  KernelChoice c{kFamNone, 0, 0};
+  if (enc0_fwd_choose(d, &c)) return c;                    // first encoder layer of the bf16 plans, on the fp32 spectrum (enc0.hip)
+  if (d.flags & (kRunEnc0 | kRunDyFromBn)) return c;       // ... declined: refused
+  if (cgemm256_choose(d, &c)) return c;                    // wide-tile kernel for the N >= 128 bf16 layers (cgemm256.hip)
+  if (thin_mask_choose(d, &c)) return c;                   // frame-staged kernels for the mask layer and its input gradient (thin_mask.hip)
+  if (thin_stage_choose(d, &c)) return c;                  // ... for the phase-merged thin layers with statistics rows (thin_stage.hip)
+  if (thin_stage64_choose(d, &c)) return c;                // ... for the 64-channel strided layers with 128 columns (thin_stage.hip)
+  if (rundirect_choose(d, &c)) return c;                   // direct-operand kernel for the thin bf16 layers (thin.hip)
+  if (rungemm_persist_choose(d, &c)) return c;             // bf16, aligned in and out, plain epilogue, enough tiles (rungemm_persist.hip)
+  c.family = kFamTiled;
+  return c;
 }
 
-// The same decisions as launch_rungemm, without a launch (sefd_plan_op_info; the per-launch knobs are read as a launch would read them now)
-int rungemm_family(const RunGemm& d) {
-  if ((d.flags & kRunEnc0) && enc0_accepts(d, false)) return kFamEnc0;
-  if (d.flags & (kRunEnc0 | kRunDyFromBn)) return kFamNone;
-  if (d.flags & kRunWTile32) return kFamCgemm256;
-  if (thin_mask_grid(d) > 0) return kFamThinMask;
-  if (thin_stage_grid(d) > 0) return kFamThinStage;
-  if (thin_stage64_grid(d) > 0) return kFamThinStage64;
-  if (rundirect_takes(d)) return kFamDirect;
-  if (d.xdt == DT_BF16 && rungemm_persist_grid(d) > 0) return kFamPersist;
-  return kFamTiled;
+void launch_rungemm(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
+  const KernelChoice c = choose_rungemm(d);
+  switch (c.family) {
+    case kFamEnc0: enc0_fwd_launch(d, c, ab, st); return;
+    case kFamCgemm256: cgemm256_launch(d, c, ab, st); return;
+    case kFamThinMask: thin_mask_launch(d, c, ab, st); return;
+    case kFamThinStage: case kFamThinStage64: thin_stage_launch(d, c, ab, st); return;
+    case kFamDirect: rundirect_launch(d, c, ab, st); return;
+    case kFamPersist: rungemm_persist_launch(d, c, ab, st); return;
+    case kFamTiled: d.xdt == DT_BF16 ? launch_rungemm_t<bf16_t>(d, ab, st) : launch_rungemm_t<float>(d, ab, st); return;
+  }
+  refuse_launch(ab, st);                                   // kFamNone
 }
+
+// The family of the choice a launch would make now (sefd_plan_op_info; the per-launch knobs are read as a launch would read them)
+int rungemm_family(const RunGemm& d) { return choose_rungemm(d).family; }
 
 // 256 x 256 tile, 8 waves, dual form of the 4-stage ring of 32 KB = 128 KB: one workgroup per CU (wgrad_tn == 256)
 static void launch_wgrad_wide(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
@@ -1334,55 +1337,55 @@ static void launch_wgrad_dma(const RunGemm& d, const ArenaBases& ab, hipStream_t
   hipLaunchKernelGGL((wgrad_bf16_dma_kernel<TN, 3>), grid, dim3(256), 0, st, d, ab);
 }
 
+// THE order in which the WGRAD families are asked.  kWgFamNone: refused.  The kernels of this file derive their grids from the descriptor.
+static KernelChoice choose_wgrad(const RunGemm& d) {
+  KernelChoice c{kWgFamNone, 0, 0};
+  if (enc0_wgrad_choose(d, &c)) return c;                  // the first layer's weight gradient on the spectrum (enc0.hip)
+  if (d.flags & (kRunEnc0 | kRunDyFromBn)) return c;       // ... declined: refused
+  if ((d.flags & kRunRank) && wgrad_rank_form(d)) { c.family = kWgFamRank; return c; }      // N <= 4 outputs over a contiguous array
+  if (d.xdt == DT_BF16 && (d.flags & kRunAligned)) {
+    if (d.flags & kRunWgWide) { c.family = d.Npad % 256 != 0 ? kWgFamWide128 : (d.flags & kRunOnesMfma) ? kWgFamWide256Ones : kWgFamWide256; return c; }
+    if (thin_wgrad_choose(d, &c)) return c;                // frame-staged kernel for the thin layers next to the mask layer (thin_wgrad.hip)
+    const int tn = wgrad_tn(d.xdt, d.N, d.Npad);           // sefd_desc.h: the planner sized nsplit for the same tile (32, 64 or 128)
+    c.family = tn == 128 ? kWgFamDma128 : tn == 64 ? kWgFamDma64 : kWgFamDma32;
+    return c;
+  }
+  c.family = d.xdt != DT_BF16 ? kWgFamF32 : d.Npad >= 128 ? kWgFamBf16_128 : kWgFamBf16_64;
+  return c;
+}
+
+template <int TN>
+static void launch_wgrad_bf16(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
+  dim3 grid(((d.Npad + TN - 1) / TN) * ((d.ldw + kWgTK - 1) / kWgTK) * d.nsplit);
+  hipLaunchKernelGGL((wgrad_bf16_kernel<TN>), grid, dim3(256), 0, st, d, ab);
+}
+
 void launch_wgrad(const RunGemm& d0, const ArenaBases& ab, hipStream_t st) {
-  if (launch_enc0_wgrad(d0, ab, st)) return;               // ... and its weight gradient
-  if (d0.flags & (kRunEnc0 | kRunDyFromBn)) { refuse_launch(ab, st); return; }
-  if (launch_wgrad_rank(d0, ab, st)) return;               // N <= 4 outputs over a contiguous array
+  const KernelChoice c = choose_wgrad(d0);
   RunGemm d = d0;
 #ifdef SEFD_TUNING
   // wrong-result arm (no partial-sum stores), tuning builds only (-DSEFD_TUNING): the product library has no switch that changes what a launch computes
   if (tune_int("WG_DBG", 0) & 8) d.flags |= 1 << 30;
 #endif
-  if (d.xdt == DT_BF16 && (d.flags & kRunAligned)) {
-    if (d.flags & kRunWgWide) { if (d.Npad % 256 == 0) launch_wgrad_wide(d, ab, st); else launch_wgrad_wide128(d, ab, st); return; }
-    if (launch_thin_wgrad(d0, ab, st)) return;     // frame-staged kernel for the thin layers next to the mask layer (thin_wgrad.hip)
-    switch (wgrad_tn(d.xdt, d.N, d.Npad)) {        // sefd_desc.h: the planner sized nsplit for the same tile
-      case 128: launch_wgrad_dma<128>(d, ab, st); break;
-      case 64: launch_wgrad_dma<64>(d, ab, st); break;
-      default: launch_wgrad_dma<32>(d, ab, st); break;   // (wgrad_tn returns 32, 64 or 128)
-    }
-    return;
+  switch (c.family) {
+    case kWgFamEnc0: case kWgFamEnc0Fused: enc0_wgrad_launch(d0, c, ab, st); return;
+    case kWgFamRank: launch_wgrad_rank(d0, ab, st); return;
+    case kWgFamWide256: case kWgFamWide256Ones: launch_wgrad_wide(d, ab, st); return;
+    case kWgFamWide128: launch_wgrad_wide128(d, ab, st); return;
+    case kWgFamThin: thin_wgrad_launch(d0, c, ab, st); return;
+    case kWgFamDma128: launch_wgrad_dma<128>(d, ab, st); return;
+    case kWgFamDma64: launch_wgrad_dma<64>(d, ab, st); return;
+    case kWgFamDma32: launch_wgrad_dma<32>(d, ab, st); return;
+    case kWgFamBf16_128: launch_wgrad_bf16<128>(d, ab, st); return;
+    case kWgFamBf16_64: launch_wgrad_bf16<64>(d, ab, st); return;
+    case kWgFamF32:
+      hipLaunchKernelGGL((wgrad_kernel<float>), dim3(((d.Npad + kWgTN - 1) / kWgTN) * ((d.ldw + kWgTK - 1) / kWgTK) * d.nsplit), dim3(256), 0, st, d, ab);
+      return;
   }
-  if (d.xdt == DT_BF16) {
-    if (d.Npad >= 128) {
-      dim3 grid(((d.Npad + 127) / 128) * ((d.ldw + kWgTK - 1) / kWgTK) * d.nsplit);
-      hipLaunchKernelGGL((wgrad_bf16_kernel<128>), grid, dim3(256), 0, st, d, ab);
-    } else {
-      dim3 grid(((d.Npad + 63) / 64) * ((d.ldw + kWgTK - 1) / kWgTK) * d.nsplit);
-      hipLaunchKernelGGL((wgrad_bf16_kernel<64>), grid, dim3(256), 0, st, d, ab);
-    }
-    return;
-  }
-  dim3 grid(((d.Npad + kWgTN - 1) / kWgTN) * ((d.ldw + kWgTK - 1) / kWgTK) * d.nsplit);
-  hipLaunchKernelGGL((wgrad_kernel<float>), grid, dim3(256), 0, st, d, ab);
+  refuse_launch(ab, st);                                   // kWgFamNone
 }
 
-// The same decisions as launch_wgrad, without a launch (sefd_plan_op_info)
-int wgrad_family(const RunGemm& d) {
-  if ((d.flags & kRunEnc0) && enc0_accepts(d, true)) return (d.flags & kRunDyFromBn) ? kWgFamEnc0Fused : kWgFamEnc0;
-  if (d.flags & (kRunEnc0 | kRunDyFromBn)) return kWgFamNone;
-  if ((d.flags & kRunRank) && wgrad_rank_form(d)) return kWgFamRank;
-  if (d.xdt == DT_BF16 && (d.flags & kRunAligned)) {
-    if (d.flags & kRunWgWide) return d.Npad % 256 != 0 ? kWgFamWide128 : (d.flags & kRunOnesMfma) ? kWgFamWide256Ones : kWgFamWide256;
-    if (thin_wgrad_takes(d)) return kWgFamThin;
-    switch (wgrad_tn(d.xdt, d.N, d.Npad)) {
-      case 128: return kWgFamDma128;
-      case 64: return kWgFamDma64;
-      default: return kWgFamDma32;
-    }
-  }
-  if (d.xdt == DT_BF16) return d.Npad >= 128 ? kWgFamBf16_128 : kWgFamBf16_64;
-  return kWgFamF32;
-}
+// The family of the choice a launch would make now (sefd_plan_op_info)
+int wgrad_family(const RunGemm& d) { return choose_wgrad(d).family; }
 
 }  // namespace sefd

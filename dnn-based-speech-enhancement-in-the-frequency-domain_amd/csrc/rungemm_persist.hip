@@ -15,6 +15,7 @@
 #include "sefd_desc.h"
 #include "tuning.h"
 #include "dev_common.h"
+#include "launch_common.h"
 
 namespace sefd {
 
@@ -313,63 +314,33 @@ static bool persist_form(const RunGemm& d) {
   return d.nseg > 0 && d.M > 0;
 }
 
-template <int BN>
-static int persist_wgs_per_cu() {
-  // resident workgroups per CU from the occupancy query, never more than the LDS admits; without a device (plan inspection on the host): the LDS bound
-  static const int n = [] {
-    const int cap = (160 * 1024) / persist_lds_bytes(BN);
-    int q = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void*>(&rungemm_persist_kernel<BN>), 256, 0) != hipSuccess || q <= 0) {
-      (void)hipGetLastError();
-      return cap;
-    }
-    return q < cap ? q : cap;
-  }();
-  return n;
-}
+// The instantiated tile widths (bn_of); a row's residency is the occupancy query's, never more than the LDS admits - which is also the value without a device
+struct PersistRow { int bn; GemmKernel kern; };
+static constexpr PersistRow kPersistRows[] = {{128, &rungemm_persist_kernel<128>}, {64, &rungemm_persist_kernel<64>}, {32, &rungemm_persist_kernel<32>}};
+static std::atomic<int> g_persist_resident[3];
 
-static int persist_cus() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
-      (void)hipGetLastError();
-      return 256;
-    }
-    return n;
-  }();
-  return ncu;
-}
-
-// Grid of the persistent launch of `d`, 0: the launch stays on rungemm_kernel.  Knobs, read per launch: RG_PERSIST 0 off, 1 the default rule, 2 every
-// launch of the form above, 3 the default rule for launches with statistics only; RG_PERSIST_GRID 0 = resident workgroups, else a forced grid
-// (the tests walk all tiles with 1 and 3 workgroups).
-int rungemm_persist_grid(const RunGemm& d) {
+// Knobs, read per launch (launch_common.h): RG_PERSIST 0 off, 1 the default rule, 2 every launch of the form above, 3 the default rule for launches
+// with statistics only; RG_PERSIST_GRID.  A workgroup's units are the 128-row tiles.
+bool rungemm_persist_choose(const RunGemm& d, KernelChoice* c) {
   const int mode = (int)tune_int("RG_PERSIST", 1);
-  if (mode <= 0 || !persist_form(d)) return 0;
-  const int bn = bn_of(d.N);
+  if (mode <= 0 || !persist_form(d)) return false;
+  const int bn = bn_of(d.N), form = bn == 128 ? 0 : bn == 64 ? 1 : 2;
   const int64_t tiles = (int64_t)((d.M + kBM - 1) / kBM) * (d.Npad / bn);
-  const int per_cu = bn == 128 ? persist_wgs_per_cu<128>() : bn == 64 ? persist_wgs_per_cu<64>() : persist_wgs_per_cu<32>();
-  int64_t grid = (int64_t)per_cu * persist_cus();
-  const int64_t forced = tune_int("RG_PERSIST_GRID", 0);
-  if (forced > 0) grid = forced;
+  const int cap = (160 * 1024) / persist_lds_bytes(bn);
+  const int64_t grid = knob_grid(tune_int("RG_PERSIST_GRID", 0), resident_wgs_per_cu(g_persist_resident[form], kPersistRows[form].kern, 256, cap, cap));
   if (mode != 2) {
     // default rule: a launch must fill the grid at least twice, or the workgroups' second tiles - where the overlap is - do not exist; and the
     // 32-wide tile stays on rungemm_kernel: its epilogue is a quarter of the 128-wide one's, and the mask layer (N = 16, 15 488 tiles) measured
     // 187 -> 198 us alone in the persistent form (profiles/rungemm_persist_notes.md)
-    if (tiles < 2 * grid || bn < 64) return 0;
-    if (mode == 3 && d.stats.arena < 0) return 0;      // measurement arm: the forward layers (they carry statistics) only
+    if (tiles < 2 * grid || bn < 64) return false;
+    if (mode == 3 && d.stats.arena < 0) return false;  // measurement arm: the forward layers (they carry statistics) only
   }
-  return (int)(tiles < grid ? tiles : grid);
+  *c = KernelChoice{kFamPersist, form, cap_grid(grid, tiles)};
+  return true;
 }
 
-bool launch_rungemm_persist(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  const int grid = rungemm_persist_grid(d);
-  if (grid <= 0) return false;
-  const int bn = bn_of(d.N);
-  if (bn == 128) hipLaunchKernelGGL((rungemm_persist_kernel<128>), dim3(grid), dim3(256), 0, st, d, ab);
-  else if (bn == 64) hipLaunchKernelGGL((rungemm_persist_kernel<64>), dim3(grid), dim3(256), 0, st, d, ab);
-  else hipLaunchKernelGGL((rungemm_persist_kernel<32>), dim3(grid), dim3(256), 0, st, d, ab);
-  return true;
+void rungemm_persist_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st) {
+  hipLaunchKernelGGL(kPersistRows[c.form].kern, dim3(c.grid), dim3(256), 0, st, d, ab);
 }
 
 }  // namespace sefd

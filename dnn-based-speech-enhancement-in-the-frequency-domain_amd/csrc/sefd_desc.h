@@ -547,7 +547,7 @@ SEFD_HD inline bool enc0_form(const RunGemm& d) {
          d.seg[0].dt == -1 && d.seg[1].dt == 0 && d.seg[0].off == -4 && d.seg[1].off == -4 && d.fstride[0] == 4 && d.base[0] == 4 && d.rowlen[0] == 512 &&
          d.Fo == 128 && d.tstride[0] == 516 && (d.N == 16 || d.N == 32 || d.N == 64) && d.n2 == 0;
 }
-// What launch_enc0_fwd (RUNGEMM) / launch_enc0_wgrad (WGRAD) execute.  No other kernel reads kRunEnc0 or kRunDyFromBn, so a descriptor that
+// What enc0_fwd_choose (RUNGEMM) / enc0_wgrad_choose (WGRAD) take.  No other kernel reads kRunEnc0 or kRunDyFromBn, so a descriptor that
 // carries either flag MUST pass this: the planner refuses a plan where one does not, the host simulator fails its run, and the launchers
 // raise the plan's status word instead of launching a generic kernel that would ignore the flags.
 SEFD_HD inline bool enc0_accepts(const RunGemm& d, bool wgrad) {

@@ -240,9 +240,15 @@ __global__ __launch_bounds__(kThinWaves * 64) void rundirect_kernel(const RunGem
 
 }  // namespace
 
+// The instantiations: form = 2 * (NI - 1) + (BNB ? 0 : 1)
+using DirectKernel = void (*)(const RunGemm, const ArenaBases, const int);
+static constexpr DirectKernel kDirectKernels[] = {&rundirect_kernel<1, true>, &rundirect_kernel<1, false>, &rundirect_kernel<2, true>, &rundirect_kernel<2, false>};
+
 // Chosen by shape: bf16 in / out, LDS-DMA-able (aligned) runs, no accumulate / ReLU, N <= 64 and the packed weights fit LDS next to the
-// staging pieces.  *wpitch_out / *lds_out: the weight row pitch and the LDS bytes of the launch.
-static bool rundirect_form(const RunGemm& d, int* wpitch_out, size_t* lds_out) {
+// staging pieces.
+static size_t rundirect_lds(const RunGemm& d) { return (size_t)d.Npad * (d.ldw * 2 + 16) + kThinWaves * 2048; }   // weight rows of ldw * 2 + 16 bytes, 2 KB per wave
+
+bool rundirect_choose(const RunGemm& d, KernelChoice* c) {
   // measured (profiles/r03_tuning_notes.md): fragment-shaped loads run at the line rate of the vector memory pipe (32 rows x 32 B per
   // instruction: ~6 TB/s of operand bytes), so the kernel wins only where K is tiny (enc0, the mask layer's input gradient: ldw = 128,
   // 92 -> 64-72 us) and loses from K = 320 on (dec4: 139 -> 255 us); larger K stays on the tiled LDS-DMA kernel
@@ -251,28 +257,16 @@ static bool rundirect_form(const RunGemm& d, int* wpitch_out, size_t* lds_out) {
   if (d.xdt != DT_BF16 || d.ydt != DT_BF16 || !(d.flags & kRunAligned) || !(d.flags & kRunYAligned)) return false;
   if ((d.flags & (kRunAccum | kRunRelu | kRunWTile32)) || d.Npad > 64 || d.ldw > kDirectMaxK || d.M < minm || d.ldw % 8 != 0) return false;
   for (int s = 0; s < d.nseg; ++s) if (d.seg[s].src < 0 || d.seg[s].len % 8 != 0) return false;
-  const int wpitch = d.ldw * 2 + 16;
-  const size_t lds = (size_t)d.Npad * wpitch + kThinWaves * 2048;
-  if (lds > 100 * 1024) return false;
-  *wpitch_out = wpitch; *lds_out = lds;
+  if (rundirect_lds(d) > 100 * 1024) return false;
+  const int blocks = (d.M + kThinRows - 1) / kThinRows;
+  *c = KernelChoice{kFamDirect, 2 * (d.Npad == 32 ? 0 : 1) + ((d.flags & kRunBnBwd) ? 0 : 1), (blocks + kThinWaves - 1) / kThinWaves};
   return true;
 }
-bool rundirect_takes(const RunGemm& d) { int wp; size_t lds; return rundirect_form(d, &wp, &lds); }   // (rungemm_family, rungemm.hip)
 
-bool launch_rundirect(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  int wpitch = 0;
-  size_t lds = 0;
-  if (!rundirect_form(d, &wpitch, &lds)) return false;
-  const int blocks = (d.M + kThinRows - 1) / kThinRows;
-  const dim3 grid((blocks + kThinWaves - 1) / kThinWaves);
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    hipLaunchKernelGGL(kern, grid, dim3(kThinWaves * 64), lds, st, d, ab, wpitch);
-  };
-  const bool bnb = (d.flags & kRunBnBwd) != 0;
-  if (d.Npad == 32) { if (bnb) go(&rundirect_kernel<1, true>); else go(&rundirect_kernel<1, false>); }
-  else { if (bnb) go(&rundirect_kernel<2, true>); else go(&rundirect_kernel<2, false>); }
-  return true;
+void rundirect_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st) {
+  const DirectKernel kern = kDirectKernels[c.form];
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
+  hipLaunchKernelGGL(kern, dim3(c.grid), dim3(kThinWaves * 64), rundirect_lds(d), st, d, ab, d.ldw * 2 + 16);
 }
 
 }  // namespace sefd

@@ -23,6 +23,8 @@
 #include "sefd_desc.h"
 #include "tuning.h"
 #include "dev_common.h"
+#include "launch_common.h"
+#include "thin_common.h"
 
 namespace sefd {
 
@@ -32,11 +34,6 @@ constexpr int kMaskFo = 128;                    // output positions per frame th
 constexpr int64_t kThinMaskMinRows = 262144;    // default rule: smaller launches stay on the kernels they had
 
 __device__ __forceinline__ int fdivm(int x, uint32_t m, uint32_t s) { return m ? (int)(__umulhi((uint32_t)x, m) >> s) : x; }
-
-// every accumulator through ONE statement behind 16 wait states before the epilogue packs it (lstm_rows.hip mfma_settle: the packing is inline
-// assembly, which the compiler's MFMA hazard padding does not see)
-__device__ __forceinline__ void settle(f32x4& a, f32x4& b) { asm volatile("s_nop 7\n\ts_nop 7" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ void settle(f32x4& a, f32x4& b, f32x4& c, f32x4& e) { asm volatile("s_nop 7\n\ts_nop 7" : "+v"(a), "+v"(b), "+v"(c), "+v"(e)); }
 
 // ------------------------------------------------------------------------------------------------------------ forward
 // C: channels per source (two sources).  LDS image of a frame: [Fo + 2 positions][2 C channels] bf16, position index = input bin + 1, the 16-byte chunk c
@@ -261,12 +258,10 @@ __global__ __launch_bounds__(256) void thin_mask_dgrad_kernel(const RunGemm d, c
 // ------------------------------------------------------------------------------------------------------------ selection
 namespace {
 
-// What both forms share: bf16 in and out, 16-byte aligned runs and output rows, a plain epilogue without statistics.
+// What both forms share: thin_common.h's plain bf16 launch, without statistics, in whole frames.
 bool mask_common(const RunGemm& d) {
-  if (d.xdt != DT_BF16 || d.ydt != DT_BF16 || !(d.flags & kRunAligned) || !(d.flags & kRunYAligned)) return false;
-  if (d.flags & (kRunAccum | kRunRelu | kRunBnBwd | kRunWTile32 | kRunEnc0 | kRunDyFromBn | kRunRank)) return false;
-  if (d.stats.arena >= 0 || d.zero.arena < 0 || d.M <= 0 || d.Tout <= 0 || d.Fo <= 0 || (int64_t)d.M % ((int64_t)d.Tout * d.Fo) != 0) return false;
-  return d.y_fstride % 8 == 0 && d.y_off % 8 == 0 && d.y_tstride % 8 == 0 && d.y_bstride % 8 == 0 && d.ldw % 8 == 0;
+  if (!thin_plain_bf16(d)) return false;
+  return d.stats.arena < 0 && d.zero.arena >= 0 && d.M > 0 && d.Tout > 0 && d.Fo > 0 && (int64_t)d.M % ((int64_t)d.Tout * d.Fo) == 0;
 }
 
 // Forward: the phase-merged transposed conv of a layer without statistics - two sources of C channels each, runs (source 0 frame u, frame u - 1, source 1
@@ -297,65 +292,43 @@ int mask_dgrad_form(const RunGemm& d) {
   return d.N / 16;
 }
 
-int mask_cus() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
-      (void)hipGetLastError();
-      return 256;
-    }
-    return n;
-  }();
-  return ncu;
-}
+// The instantiated forms.  fwd: the forward with key = C channels per source; else the input gradient with key = 16-column tiles.
+struct MaskRow { bool fwd; int key; GemmKernel kern; int fallback; };      // fallback: resident workgroups per CU without a device
+constexpr MaskRow kMaskRows[] = {
+    {true, 32, &thin_mask_fwd_kernel<32>, 3},
+    {true, 16, &thin_mask_fwd_kernel<16>, 6},
+    {false, 4, &thin_mask_dgrad_kernel<4>, 4},
+    {false, 2, &thin_mask_dgrad_kernel<2>, 4},
+};
+constexpr int kMaskForms = sizeof(kMaskRows) / sizeof(kMaskRows[0]);
+std::atomic<int> g_mask_resident[kMaskForms];
 
-// resident workgroups per CU of `kern` from the occupancy query; without a device (plan inspection on the host): `fallback`
-template <typename K>
-int mask_wgs_per_cu(K kern, int fallback) {
-  int q = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void*>(kern), 256, 0) != hipSuccess || q <= 0) {
-    (void)hipGetLastError();
-    return fallback;
-  }
-  return q;
-}
-
-int mask_resident(int cf, int nt) {
-  if (cf == 32) { static const int n = mask_wgs_per_cu(&thin_mask_fwd_kernel<32>, 3); return n; }
-  if (cf == 16) { static const int n = mask_wgs_per_cu(&thin_mask_fwd_kernel<16>, 6); return n; }
-  if (nt == 4) { static const int n = mask_wgs_per_cu(&thin_mask_dgrad_kernel<4>, 4); return n; }
-  static const int n = mask_wgs_per_cu(&thin_mask_dgrad_kernel<2>, 4);
-  return n;
+// Row of kMaskRows that runs `d`, -1: neither form
+int mask_form(const RunGemm& d) {
+  const int cf = mask_fwd_form(d), nt = cf ? 0 : mask_dgrad_form(d);
+  if (!cf && !nt) return -1;
+  for (int i = 0; i < kMaskForms; ++i)
+    if (kMaskRows[i].fwd == (cf != 0) && kMaskRows[i].key == (cf ? cf : nt)) return i;
+  return -1;
 }
 
 }  // namespace
 
-// Grid of the frame-staged launch of `d`, 0: the launch stays where it was.  Knobs, read per launch: THIN_MASK 0 off, 1 the default rule (launches of at
-// least kThinMaskMinRows rows), 2 every launch of either form; THIN_MASK_GRID 0 = resident workgroups, else a forced grid (the tests walk all frames
-// with 1 and 3 workgroups).
-int thin_mask_grid(const RunGemm& d) {
+// Knobs, read per launch (launch_common.h): THIN_MASK with the default rule "launches of at least kThinMaskMinRows rows", THIN_MASK_GRID.
+// A workgroup's units: frames (forward); blocks of 16 rows, four waves a workgroup (input gradient).
+bool thin_mask_choose(const RunGemm& d, KernelChoice* c) {
   const int mode = (int)tune_int("THIN_MASK", 1);
-  if (mode <= 0) return 0;
-  const int cf = mask_fwd_form(d), nt = cf ? 0 : mask_dgrad_form(d);
-  if (!cf && !nt) return 0;
-  if (mode != 2 && d.M < kThinMaskMinRows) return 0;
-  const int64_t units = cf ? d.M / kMaskFo : (((int64_t)d.M + 15) / 16 + 3) / 4;      // frames; blocks of 16 rows, four waves a workgroup
-  int64_t grid = (int64_t)mask_resident(cf, nt) * mask_cus();
-  const int64_t forced = tune_int("THIN_MASK_GRID", 0);
-  if (forced > 0) grid = forced;
-  if (grid > units) grid = units;
-  return (int)(grid < 1 ? 1 : grid);
+  if (mode <= 0) return false;
+  const int form = mask_form(d);
+  if (form < 0 || !knob_takes(mode, d.M >= kThinMaskMinRows)) return false;
+  const MaskRow& r = kMaskRows[form];
+  const int64_t units = r.fwd ? d.M / kMaskFo : (((int64_t)d.M + 15) / 16 + 3) / 4;
+  *c = KernelChoice{kFamThinMask, form, cap_grid(knob_grid(tune_int("THIN_MASK_GRID", 0), resident_wgs_per_cu(g_mask_resident[form], r.kern, 256, r.fallback)), units)};
+  return true;
 }
 
-bool launch_thin_mask(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  const int grid = thin_mask_grid(d);
-  if (grid <= 0) return false;
-  const int cf = mask_fwd_form(d);
-  if (cf == 32) hipLaunchKernelGGL((thin_mask_fwd_kernel<32>), dim3(grid), dim3(256), 0, st, d, ab);
-  else if (cf == 16) hipLaunchKernelGGL((thin_mask_fwd_kernel<16>), dim3(grid), dim3(256), 0, st, d, ab);
-  else if (mask_dgrad_form(d) == 4) hipLaunchKernelGGL((thin_mask_dgrad_kernel<4>), dim3(grid), dim3(256), 0, st, d, ab);
-  else hipLaunchKernelGGL((thin_mask_dgrad_kernel<2>), dim3(grid), dim3(256), 0, st, d, ab);
-  return true;
+void thin_mask_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st) {
+  hipLaunchKernelGGL(kMaskRows[c.form].kern, dim3(c.grid), dim3(256), 0, st, d, ab);
 }
 
 }  // namespace sefd

@@ -29,18 +29,16 @@
 #include "sefd_desc.h"
 #include "tuning.h"
 #include "dev_common.h"
+#include "launch_common.h"
+#include "thin_common.h"
 
 namespace sefd {
 
 namespace {
 
 constexpr int kStageFo = 64;                     // output positions per frame the kernel is built for
-constexpr int kStage64Fo = 32;                   // ... of the strided form at 64 channels (thin_stage64_grid)
+constexpr int kStage64Fo = 32;                   // ... of the strided form at 64 channels (thin_stage64_choose)
 constexpr int64_t kThinStageMinRows = 262144;    // default rule: smaller launches stay on the kernels they had
-
-// every accumulator through ONE statement behind 16 wait states before the epilogue reads it in inline assembly (thin_mask.hip settle)
-__device__ __forceinline__ void settle(f32x4& a, f32x4& b) { asm volatile("s_nop 7\n\ts_nop 7" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ void settle(f32x4& a, f32x4& b, f32x4& c, f32x4& e) { asm volatile("s_nop 7\n\ts_nop 7" : "+v"(a), "+v"(b), "+v"(c), "+v"(e)); }
 
 // Statistics in the order of the kernels replaced (rungemm_persist.hip, rungemm_kernel), so that the partial rows - and with them every step of a training
 // run - keep their bits: a 128-row statistics block is four groups of 32 rows; in a group a column has two chains (rows 4 hh + 8 k + r, k and r
@@ -48,10 +46,6 @@ __device__ __forceinline__ void settle(f32x4& a, f32x4& b, f32x4& c, f32x4& e) {
 // sums added in ascending order to 0.f.  Here a group is two 16-position blocks (a, b) with one row per lane li, so a chain walks the lanes 4 hh .. + 3,
 // 8 + 4 hh .. + 3 of block a and then of block b: the running value moves from lane to lane by DPP row shifts (all q rows of the wave in step).  The
 // group's sum and sum of squares arrive in lane li == 11; the other lanes hold values nobody reads.
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
 __device__ __forceinline__ void chain32(float a, float b, float& t1, float& t2) {
   constexpr int SHR1 = 0x111, SHR5 = 0x115, SHL11 = 0x10B, SHL4 = 0x104;     // row_shr:n lane i <- lane i - n; row_shl:n lane i <- lane i + n
   float s = 0.f + a, r = __builtin_fmaf(a, a, 0.f);
@@ -297,7 +291,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void t
 //   * wave w: column pair w % NCP, position group w / NCP: half a frame (two blocks of 16 positions), the whole frame at NCP = 4.  At NCP = 1 (the
 //     small plans' forward) the waves 2 and 3 only load;
 //   * FO, the output positions per frame, is a parameter of the geometry.  <64, 4, 32> is the next class up (profiles/thin_stage64_notes.md; selected by
-//     thin_stage64_grid under a knob of its own): 64 channels, 128 columns, K = 640 - the third encoder layer's forward conv and the two input gradients
+//     thin_stage64_choose under a knob of its own): 64 channels, 128 columns, K = 640 - the third encoder layer's forward conv and the two input gradients
 //     of the third-to-last decoder layer.  Four waves x 32 columns hold the 160 KB of weights in 160 registers each (two workgroups per CU); per wave and
 //     frame the MFMAs (80) and the fragment reads (40) are those of <32, 4, 64>.  A statistics row is four frames there.
 namespace {
@@ -566,12 +560,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCP == 4 ? 
 // ------------------------------------------------------------------------------------------------------------ selection
 namespace {
 
-// What all forms share: bf16 in and out, 16-byte aligned runs and output rows, a plain epilogue (bias, optional statistics), Fo = `fo`, whole frames.
+// The instantiated forms.  strided: the strided form with n = NCP pairs of 32 columns, else the phase-merged form with n = NSRC sources; C channels
+// per source and position; fo output positions per frame.  The last row is a family of its own (thin_stage64_choose).
+struct StageRow { bool strided; int C, n, fo; GemmKernel kern; int fallback; };      // fallback: resident workgroups per CU without a device
+constexpr StageRow kStageRows[] = {
+    {false, 64, 2, kStageFo, &thin_stage_pm_kernel<64, 2>, 2},
+    {false, 64, 1, kStageFo, &thin_stage_pm_kernel<64, 1>, 2},
+    {false, 32, 2, kStageFo, &thin_stage_pm_kernel<32, 2>, 4},
+    {false, 32, 1, kStageFo, &thin_stage_pm_kernel<32, 1>, 4},
+    {true, 32, 2, kStageFo, &thin_stage_st_kernel<32, 2>, 3},
+    {true, 32, 4, kStageFo, &thin_stage_st_kernel<32, 4>, 2},
+    {true, 16, 1, kStageFo, &thin_stage_st_kernel<16, 1>, 4},
+    {true, 16, 2, kStageFo, &thin_stage_st_kernel<16, 2>, 4},
+    {true, 64, 4, kStage64Fo, &thin_stage_st_kernel<64, 4, kStage64Fo>, 2},
+};
+constexpr int kStageForms = sizeof(kStageRows) / sizeof(kStageRows[0]);
+std::atomic<int> g_stage_resident[kStageForms];
+
+// Row of kStageRows with these parameters, -1: a form that is not built
+int stage_row(bool strided, int C, int n, int fo) {
+  for (int i = 0; i < kStageForms; ++i)
+    if (kStageRows[i].strided == strided && kStageRows[i].C == C && kStageRows[i].n == n && kStageRows[i].fo == fo) return i;
+  return -1;
+}
+
+// What all forms share: thin_common.h's plain bf16 launch (bias, optional statistics), Fo = `fo`, whole frames.
 bool stage_common(const RunGemm& d, int fo = kStageFo) {
-  if (d.xdt != DT_BF16 || d.ydt != DT_BF16 || !(d.flags & kRunAligned) || !(d.flags & kRunYAligned)) return false;
-  if (d.flags & (kRunAccum | kRunRelu | kRunBnBwd | kRunWTile32 | kRunEnc0 | kRunDyFromBn | kRunRank)) return false;
+  if (!thin_plain_bf16(d)) return false;
   if (d.zero.arena < 0 || d.M <= 0 || d.Tout <= 0 || d.Fo != fo || (int64_t)d.M % ((int64_t)d.Tout * d.Fo) != 0 || d.x[0].arena < 0) return false;
-  if (d.y_fstride % 8 != 0 || d.y_off % 8 != 0 || d.y_tstride % 8 != 0 || d.y_bstride % 8 != 0 || d.ldw % 8 != 0) return false;
   if (d.n2 != 0 && (d.n2 < 0 || d.n2 % 8 != 0 || d.n2 >= d.N || d.y2.arena < 0)) return false;
   if (d.stats.arena >= 0 && (d.Npad != d.N || d.n2 != 0 || d.stats.off % 16 != 0)) return false;   // every column of a statistics row is written
   return d.Tin[0] > 0 && d.tstride[0] % 8 == 0 && d.base[0] % 8 == 0 && d.bstride[0] % 8 == 0;
@@ -591,141 +607,79 @@ bool stage_runs(const RunGemm& d, int nsrc, int off, int len) {
 }
 
 // The phase-merged form with N = C: one or two sources of C channels per position, per source two runs of 3 positions from bin f - 1.
-// Returns C + 256 * sources, 0: not this form or a C that is not built.
+// Returns its row, -1: not this form or a (C, sources) that is not built.
 int stage_pm_form(const RunGemm& d) {
-  if (!stage_common(d) || d.n2 != 0) return 0;
+  if (!stage_common(d) || d.n2 != 0) return -1;
   const int nsrc = d.x[1].arena >= 0 ? 2 : 1, C = d.fstride[0];
-  if ((C != 64 && C != 32) || d.N != C) return 0;                                                   // the instantiated channel counts
+  const int row = stage_row(false, C, nsrc, kStageFo);
+  if (row < 0 || d.N != C) return -1;
   for (int s = 0; s < nsrc; ++s)
-    if (d.fstride[s] != C || d.rowlen[s] != d.Fo * C || d.Tin[s] != d.Tin[0] || d.tstride[s] % 8 != 0 || d.base[s] % 8 != 0 || d.bstride[s] % 8 != 0) return 0;
-  return stage_runs(d, nsrc, -C, 3 * C) ? C + 256 * nsrc : 0;
+    if (d.fstride[s] != C || d.rowlen[s] != d.Fo * C || d.Tin[s] != d.Tin[0] || d.tstride[s] % 8 != 0 || d.base[s] % 8 != 0 || d.bstride[s] % 8 != 0) return -1;
+  return stage_runs(d, nsrc, -C, 3 * C) ? row : -1;
 }
 
 // The strided form: one source of C channels per position, 2 Fo positions per frame, two runs of 5 positions from position 2 f - 2, 32 NCP columns,
 // with statistics rows (the encoder forward) or split over two destinations (the decoder's merged input gradient).
-// Returns C + 256 * NCP, 0: not this form or a (C, NCP) that is not built.
+// Returns its row, -1: not this form or a (C, NCP) that is not built.
 int stage_st_form(const RunGemm& d) {
-  if (!stage_common(d) || d.x[1].arena >= 0 || d.fstride[0] % 2 != 0 || d.N % 32 != 0) return 0;
-  const int C = d.fstride[0] / 2, ncp = d.N / 32;
-  if (!((C == 32 && (ncp == 2 || ncp == 4)) || (C == 16 && (ncp == 1 || ncp == 2)))) return 0;      // the instantiated forms
-  if (d.rowlen[0] != 2 * d.Fo * C) return 0;
-  if (d.stats.arena < 0 && d.n2 == 0) return 0;      // the forward with its statistics rows or the two-destination gradient: what was measured
-  return stage_runs(d, 1, -2 * C, 5 * C) ? C + 256 * ncp : 0;
+  if (!stage_common(d) || d.x[1].arena >= 0 || d.fstride[0] % 2 != 0 || d.N % 32 != 0) return -1;
+  const int C = d.fstride[0] / 2;
+  const int row = stage_row(true, C, d.N / 32, kStageFo);
+  if (row < 0 || d.rowlen[0] != 2 * d.Fo * C) return -1;
+  if (d.stats.arena < 0 && d.n2 == 0) return -1;     // the forward with its statistics rows or the two-destination gradient: what was measured
+  return stage_runs(d, 1, -2 * C, 5 * C) ? row : -1;
 }
 
-// 0: neither form; else the phase-merged form's value, or the strided form's + 65536
+// Row of either form at Fo = 64, -1: neither
 int stage_form(const RunGemm& d) {
   const int pm = stage_pm_form(d);
-  if (pm) return pm;
-  const int st = stage_st_form(d);
-  return st ? st + 65536 : 0;
+  return pm >= 0 ? pm : stage_st_form(d);
 }
 
 // The strided form at 64 channels and 32 output positions per frame, 128 columns (thin_stage_st_kernel<64, 4, 32>): the third encoder layer's forward
 // conv (bias, statistics rows) and the input gradients of the third-to-last decoder layer, one launch per destination (no statistics; a second
 // destination at n2 costs the kernel nothing and is allowed).  Field by field, as stage_st_form; no flag but the two alignment flags.
-bool stage64_form(const RunGemm& d) {
-  if (!stage_common(d, kStage64Fo) || (d.flags & ~(kRunAligned | kRunYAligned)) != 0 || d.x[1].arena >= 0) return false;
+// Returns its row, -1: not this form.
+int stage64_form(const RunGemm& d) {
+  if (!stage_common(d, kStage64Fo) || (d.flags & ~(kRunAligned | kRunYAligned)) != 0 || d.x[1].arena >= 0) return -1;
   constexpr int C = 64;
-  if (d.fstride[0] != 2 * C || d.N != 128 || d.Npad != 128 || d.rowlen[0] != 2 * d.Fo * C) return false;
-  if (d.stats.arena < 0 && d.bias.arena >= 0) return false;      // the two epilogues built and measured: bias + statistics, or neither
-  return stage_runs(d, 1, -2 * C, 5 * C);
+  if (d.fstride[0] != 2 * C || d.N != 128 || d.Npad != 128 || d.rowlen[0] != 2 * d.Fo * C) return -1;
+  if (d.stats.arena < 0 && d.bias.arena >= 0) return -1;         // the two epilogues built and measured: bias + statistics, or neither
+  return stage_runs(d, 1, -2 * C, 5 * C) ? stage_row(true, C, 4, kStage64Fo) : -1;
 }
 
-int stage_cus() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
-      (void)hipGetLastError();
-      return 256;
-    }
-    return n;
-  }();
-  return ncu;
+// Row that runs `d` under its family's knob at `mode` (launch_common.h; default rule: launches of at least kThinStageMinRows rows), -1: not taken
+int stage_takes(const RunGemm& d, int mode, int (*form_of)(const RunGemm&)) {
+  if (mode <= 0) return -1;
+  const int form = form_of(d);
+  return form >= 0 && knob_takes(mode, d.M >= kThinStageMinRows) ? form : -1;
 }
 
-// resident workgroups per CU of `kern` from the occupancy query; without a device (plan inspection on the host): `fallback`
-template <typename K>
-int stage_wgs_per_cu(K kern, int fallback) {
-  int q = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void*>(kern), 256, 0) != hipSuccess || q <= 0) {
-    (void)hipGetLastError();
-    return fallback;
-  }
-  return q;
+// ... and its choice with the family's grid knob at `forced`.  The unit of a workgroup's run is a statistics row: 128 / fo frames.
+KernelChoice stage_choice(const RunGemm& d, int family, int form, int64_t forced) {
+  const StageRow& r = kStageRows[form];
+  const int fpr = 128 / r.fo;
+  return KernelChoice{family, form, cap_grid(knob_grid(forced, resident_wgs_per_cu(g_stage_resident[form], r.kern, 256, r.fallback)), (d.M / r.fo + fpr - 1) / fpr)};
 }
-
-int stage_resident(int form) {
-  switch (form) {
-    case 64 + 512: { static const int n = stage_wgs_per_cu(&thin_stage_pm_kernel<64, 2>, 2); return n; }
-    case 64 + 256: { static const int n = stage_wgs_per_cu(&thin_stage_pm_kernel<64, 1>, 2); return n; }
-    case 32 + 512: { static const int n = stage_wgs_per_cu(&thin_stage_pm_kernel<32, 2>, 4); return n; }
-    case 32 + 256: { static const int n = stage_wgs_per_cu(&thin_stage_pm_kernel<32, 1>, 4); return n; }
-    case 65536 + 32 + 512: { static const int n = stage_wgs_per_cu(&thin_stage_st_kernel<32, 2>, 3); return n; }
-    case 65536 + 32 + 1024: { static const int n = stage_wgs_per_cu(&thin_stage_st_kernel<32, 4>, 2); return n; }
-    case 65536 + 16 + 256: { static const int n = stage_wgs_per_cu(&thin_stage_st_kernel<16, 1>, 4); return n; }
-    default: { static const int n = stage_wgs_per_cu(&thin_stage_st_kernel<16, 2>, 4); return n; }
-  }
-}
-
-int stage64_resident() { static const int n = stage_wgs_per_cu(&thin_stage_st_kernel<64, 4, kStage64Fo>, 2); return n; }
 
 }  // namespace
 
-// Grid of the 64-channel strided launch of `d`, 0: the launch stays where it was.  Knobs of its own, read per launch: THIN_STAGE64 0 off, 1 the default
-// rule (launches of at least kThinStageMinRows rows), 2 every launch of the form; THIN_STAGE64_GRID 0 = resident workgroups, else a forced grid.  The unit
-// of a workgroup's run is a statistics row (four frames).  THIN_STAGE and THIN_MASK do not switch it.
-int thin_stage64_grid(const RunGemm& d) {
-  const int mode = (int)tune_int("THIN_STAGE64", 1);
-  if (mode <= 0 || !stage64_form(d)) return 0;
-  if (mode != 2 && d.M < kThinStageMinRows) return 0;
-  constexpr int fpr = 128 / kStage64Fo;
-  const int64_t units = (d.M / kStage64Fo + fpr - 1) / fpr;
-  int64_t grid = (int64_t)stage64_resident() * stage_cus();
-  const int64_t forced = tune_int("THIN_STAGE64_GRID", 0);
-  if (forced > 0) grid = forced;
-  if (grid > units) grid = units;
-  return (int)(grid < 1 ? 1 : grid);
+// Knobs, read per launch: THIN_STAGE, THIN_STAGE_GRID
+bool thin_stage_choose(const RunGemm& d, KernelChoice* c) {
+  const int form = stage_takes(d, (int)tune_int("THIN_STAGE", 1), stage_form);
+  if (form >= 0) *c = stage_choice(d, kFamThinStage, form, tune_int("THIN_STAGE_GRID", 0));
+  return form >= 0;
+}
+// The 64-channel strided form: knobs of its own, THIN_STAGE64 and THIN_STAGE64_GRID.  THIN_STAGE and THIN_MASK do not switch it.
+bool thin_stage64_choose(const RunGemm& d, KernelChoice* c) {
+  const int form = stage_takes(d, (int)tune_int("THIN_STAGE64", 1), stage64_form);
+  if (form >= 0) *c = stage_choice(d, kFamThinStage64, form, tune_int("THIN_STAGE64_GRID", 0));
+  return form >= 0;
 }
 
-bool launch_thin_stage64(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  const int grid = thin_stage64_grid(d);
-  if (grid <= 0) return false;
-  hipLaunchKernelGGL((thin_stage_st_kernel<64, 4, kStage64Fo>), dim3(grid), dim3(256), 0, st, d, ab);
-  return true;
-}
-
-// Grid of the frame-staged launch of `d`, 0: the launch stays where it was.  Knobs, read per launch: THIN_STAGE 0 off, 1 the default rule (launches of at
-// least kThinStageMinRows rows), 2 every launch of the form; THIN_STAGE_GRID 0 = resident workgroups, else a forced grid (the tests walk all frames
-// with 1 and 3 workgroups).  The unit of a workgroup's run is a statistics row (two frames).
-int thin_stage_grid(const RunGemm& d) {
-  const int mode = (int)tune_int("THIN_STAGE", 1);
-  if (mode <= 0) return 0;
-  const int form = stage_form(d);
-  if (!form) return 0;
-  if (mode != 2 && d.M < kThinStageMinRows) return 0;
-  const int64_t units = (d.M / kStageFo + 1) / 2;
-  int64_t grid = (int64_t)stage_resident(form) * stage_cus();
-  const int64_t forced = tune_int("THIN_STAGE_GRID", 0);
-  if (forced > 0) grid = forced;
-  if (grid > units) grid = units;
-  return (int)(grid < 1 ? 1 : grid);
-}
-
-bool launch_thin_stage(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  const int grid = thin_stage_grid(d);
-  if (grid <= 0) return false;
-  switch (stage_form(d)) {
-    case 64 + 512: hipLaunchKernelGGL((thin_stage_pm_kernel<64, 2>), dim3(grid), dim3(256), 0, st, d, ab); break;
-    case 64 + 256: hipLaunchKernelGGL((thin_stage_pm_kernel<64, 1>), dim3(grid), dim3(256), 0, st, d, ab); break;
-    case 32 + 512: hipLaunchKernelGGL((thin_stage_pm_kernel<32, 2>), dim3(grid), dim3(256), 0, st, d, ab); break;
-    case 32 + 256: hipLaunchKernelGGL((thin_stage_pm_kernel<32, 1>), dim3(grid), dim3(256), 0, st, d, ab); break;
-    case 65536 + 32 + 512: hipLaunchKernelGGL((thin_stage_st_kernel<32, 2>), dim3(grid), dim3(256), 0, st, d, ab); break;
-    case 65536 + 32 + 1024: hipLaunchKernelGGL((thin_stage_st_kernel<32, 4>), dim3(grid), dim3(256), 0, st, d, ab); break;
-    case 65536 + 16 + 256: hipLaunchKernelGGL((thin_stage_st_kernel<16, 1>), dim3(grid), dim3(256), 0, st, d, ab); break;
-    default: hipLaunchKernelGGL((thin_stage_st_kernel<16, 2>), dim3(grid), dim3(256), 0, st, d, ab); break;
-  }
-  return true;
+// Both families: the choice's form is the row
+void thin_stage_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st) {
+  hipLaunchKernelGGL(kStageRows[c.form].kern, dim3(c.grid), dim3(256), 0, st, d, ab);
 }
 
 }  // namespace sefd

@@ -20,6 +20,8 @@
 #include "sefd_desc.h"
 #include "tuning.h"
 #include "dev_common.h"
+#include "launch_common.h"
+#include "thin_common.h"
 
 namespace sefd {
 
@@ -235,49 +237,52 @@ __global__ __launch_bounds__(256) void thin_wgrad_kernel(const RunGemm d, const 
 // ------------------------------------------------------------------------------------------------------------ selection
 namespace {
 
+// The instantiated forms: C channels per position of the run operand, N channels of the dense operand
+struct WgRow { int C, N; GemmKernel kern; };
+constexpr WgRow kThinWgRows[] = {{32, 64, &thin_wgrad_kernel<32, 64>}, {16, 32, &thin_wgrad_kernel<16, 32>}, {8, 32, &thin_wgrad_kernel<8, 32>}};
+constexpr int kThinWgForms = sizeof(kThinWgRows) / sizeof(kThinWgRows[0]);
+
 // The form: aligned bf16 WGRAD without a ones run, one run source of C channels per position and 2 Fo positions per frame, two runs (frames u + hi and
 // u + hi - 1, either order) of 5 positions from position 2 f - 2 in layout_segs' columns, a dense operand of N = Npad channels.
-// Returns C + 256 * N, 0: not this form or a (C, N) that is not built.
+// Returns the row of kThinWgRows, -1: not this form or a (C, N) that is not built.
 int wgrad_thin_form(const RunGemm& d) {
-  if (d.xdt != DT_BF16 || d.ydt != DT_BF16 || !(d.flags & kRunAligned)) return 0;
-  if (d.flags & ~(kRunAligned | kRunYAligned)) return 0;    // nothing else: no wide tile, ones MFMA, rank form, first layer, fused BatchNorm backward
-  if (d.zero.arena < 0 || d.x[0].arena < 0 || d.x[1].arena >= 0 || d.y.arena < 0 || d.w.arena < 0 || d.nseg != 2 || d.nsplit < 1) return 0;
-  if (d.fstride[0] % 2 != 0 || d.N != d.Npad) return 0;
+  if (d.xdt != DT_BF16 || d.ydt != DT_BF16 || !(d.flags & kRunAligned)) return -1;
+  if (d.flags & ~(kRunAligned | kRunYAligned)) return -1;   // nothing else: no wide tile, ones MFMA, rank form, first layer, fused BatchNorm backward
+  if (d.zero.arena < 0 || d.x[0].arena < 0 || d.x[1].arena >= 0 || d.y.arena < 0 || d.w.arena < 0 || d.nseg != 2 || d.nsplit < 1) return -1;
+  if (d.fstride[0] % 2 != 0 || d.N != d.Npad) return -1;
   const int C = d.fstride[0] / 2, N = d.N;
-  if (!((C == 32 && N == 64) || (C == 16 && N == 32) || (C == 8 && N == 32))) return 0;              // the instantiated forms
+  int row = -1;
+  for (int i = 0; i < kThinWgForms; ++i)
+    if (kThinWgRows[i].C == C && kThinWgRows[i].N == N) row = i;
+  if (row < 0) return -1;
   const int Fo = C == 8 ? 128 : 64;
-  if (d.Fo != Fo || d.Tout <= 0 || d.M <= 0 || (int64_t)d.M % ((int64_t)d.Tout * Fo) != 0 || d.Tin[0] <= 0) return 0;
-  if (d.rowlen[0] != 2 * Fo * C || d.tstride[0] % 8 != 0 || d.base[0] % 8 != 0 || d.bstride[0] % 8 != 0 || d.x[0].off % 16 != 0) return 0;
-  if (d.y_fstride % 8 != 0 || d.y_fstride < N || d.y_off % 8 != 0 || d.y_tstride % 8 != 0 || d.y_bstride % 8 != 0 || d.y.off % 16 != 0) return 0;
+  if (d.Fo != Fo || d.Tout <= 0 || d.M <= 0 || (int64_t)d.M % ((int64_t)d.Tout * Fo) != 0 || d.Tin[0] <= 0) return -1;
+  if (d.rowlen[0] != 2 * Fo * C || d.tstride[0] % 8 != 0 || d.base[0] % 8 != 0 || d.bstride[0] % 8 != 0 || d.x[0].off % 16 != 0) return -1;
+  if (!y_strides_aligned(d) || d.y_fstride < N || d.y.off % 16 != 0) return -1;
   const int hi = d.seg[0].dt > d.seg[1].dt ? d.seg[0].dt : d.seg[1].dt, lo = d.seg[0].dt < d.seg[1].dt ? d.seg[0].dt : d.seg[1].dt;
-  if (lo != hi - 1) return 0;
+  if (lo != hi - 1) return -1;
   const int pad = (5 * C + 63) / 64 * 64;
   for (int s = 0; s < 2; ++s)
-    if (d.seg[s].src != 0 || d.seg[s].off != -2 * C || d.seg[s].len != 5 * C || d.seg[s].koff != s * pad) return 0;
-  if (d.ldw != 2 * pad) return 0;
-  return C + 256 * N;
+    if (d.seg[s].src != 0 || d.seg[s].off != -2 * C || d.seg[s].len != 5 * C || d.seg[s].koff != s * pad) return -1;
+  if (d.ldw != 2 * pad) return -1;
+  return row;
 }
 
 }  // namespace
 
-// Whether launch_wgrad puts `d` on thin_wgrad_kernel.  Knob, read per launch: THIN_WGRAD 0 off, 1 the default rule (launches of a built form with at least
-// kThinWgradMinRows rows), 2 every launch of a built form.  The grid is d.nsplit (WG_NSPLIT varies it).
-bool thin_wgrad_takes(const RunGemm& d) {
+// Knob, read per launch (launch_common.h): THIN_WGRAD with the default rule "launches of a built form with at least kThinWgradMinRows rows".  The grid is
+// d.nsplit (WG_NSPLIT varies it).
+bool thin_wgrad_choose(const RunGemm& d, KernelChoice* c) {
   const int mode = (int)tune_int("THIN_WGRAD", 1);
   if (mode <= 0) return false;
-  if (!wgrad_thin_form(d)) return false;
-  return mode == 2 || d.M >= kThinWgradMinRows;
+  const int form = wgrad_thin_form(d);
+  if (form < 0 || !knob_takes(mode, d.M >= kThinWgradMinRows)) return false;
+  *c = KernelChoice{kWgFamThin, form, d.nsplit};
+  return true;
 }
 
-bool launch_thin_wgrad(const RunGemm& d, const ArenaBases& ab, hipStream_t st) {
-  if (!thin_wgrad_takes(d)) return false;
-  const dim3 grid((unsigned)d.nsplit);
-  switch (wgrad_thin_form(d)) {
-    case 32 + 256 * 64: hipLaunchKernelGGL((thin_wgrad_kernel<32, 64>), grid, dim3(256), 0, st, d, ab); break;
-    case 16 + 256 * 32: hipLaunchKernelGGL((thin_wgrad_kernel<16, 32>), grid, dim3(256), 0, st, d, ab); break;
-    default: hipLaunchKernelGGL((thin_wgrad_kernel<8, 32>), grid, dim3(256), 0, st, d, ab); break;
-  }
-  return true;
+void thin_wgrad_launch(const RunGemm& d, const KernelChoice& c, const ArenaBases& ab, hipStream_t st) {
+  hipLaunchKernelGGL(kThinWgRows[c.form].kern, dim3((unsigned)c.grid), dim3(256), 0, st, d, ab);
 }
 
 }  // namespace sefd

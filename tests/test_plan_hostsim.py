@@ -533,7 +533,7 @@ def test_syncbn_ranks_equal_big_batch_plan(model, kn, ru, dtype, world, B, L, kn
 
 def test_enc0_descriptor_predicate_fires_on_a_misaligned_copy():
     """sefd_desc.h enc0_accepts: the fused first-layer weight gradient of a real bf16 plan passes it; the same descriptor with an odd y_off
-    (which launch_enc0_wgrad declines - and no generic kernel reads kRunDyFromBn) fails it, so the host simulator would refuse to run it."""
+    (which enc0_wgrad_choose declines - and no generic kernel reads kRunDyFromBn) fails it, so the host simulator would refuse to run it."""
     from simutil import sim
     plan = Plan(2, 3000, masking_mode="C", act_dtype="bf16", **SMALL)
     sz = plan.lib.sefd_op_size()

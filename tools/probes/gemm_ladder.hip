@@ -94,7 +94,7 @@ static void launch(const RunGemm& g, int arm) {
         last = g.w.off;
       }
       launch_rungemm(o, g_ab, 0);
-    } else { g_cgemm256_dbg = arm == -1 ? 0 : -arm; if (!launch_cgemm256(g, g_ab, 0)) { fprintf(stderr, "cgemm256 refused\n"); exit(1); } }
+    } else { g_cgemm256_dbg = arm == -1 ? 0 : -arm; KernelChoice c; if (!cgemm256_choose(g, &c)) { fprintf(stderr, "cgemm256 refused\n"); exit(1); } cgemm256_launch(g, c, g_ab, 0); }
   } else if (w128) {
     RunGemm n = g;
     n.flags |= kRunWTile32;                                  // the weight bytes are random: read as K-tile major here, the old arm reads their un-tiled copy
