@@ -80,6 +80,9 @@ def lib():
         "sefd_composite_frames": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "sefd_stoi_ws_bytes": (i64, [i32, i32, i32]),
         "sefd_stoi_gpu": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+        "sefd_stoi_ws_bytes_ex": (i64, [i32, i32, i32, i32]),
+        "sefd_stoi_gpu_ex": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "sefd_stoi_backward": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),
         "sefd_pmsqe_table_floats": (i64, []),
         "sefd_pmsqe_ws_floats": (i64, [i32, i32]),
         "sefd_pmsqe_forward": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
@@ -113,6 +116,6 @@ EXPORTED = ["sefd_plan_create", "sefd_plan_destroy", "sefd_plan_error", "sefd_pl
             "sefd_plan_param_shape", "sefd_plan_buffer", "sefd_plan_num_buffers", "sefd_plan_buffer_name",
             "sefd_plan_const_data", "sefd_plan_num_ops", "sefd_plan_ops", "sefd_op_size", "sefd_plan_op_info", "sefd_plan_run",
             "sefd_plan_grad_bucket", "sefd_plan_grad_bucket_range", "sefd_plan_run_cb", "sefd_plan_run_flags", "sefd_plan_run_timed",
-            "sefd_loss_ws_floats", "sefd_loss_forward", "sefd_loss_backward", "sefd_loss_rows_ws_floats", "sefd_loss_rows_forward", "sefd_loss_rows_backward", "sefd_loss_dp_offset", "sefd_loss_dp_finish", "sefd_lms_forward", "sefd_lms_backward", "sefd_fsn_targets", "sefd_fsn_targets_backward", "sefd_norm_ws_floats", "sefd_norm_forward", "sefd_norm_backward", "sefd_unfold_forward", "sefd_unfold_backward", "sefd_mix_snr", "sefd_composite_ws_bytes", "sefd_composite_frames", "sefd_stoi_ws_bytes", "sefd_stoi_gpu", "sefd_pmsqe_table_floats", "sefd_pmsqe_ws_floats", "sefd_pmsqe_forward", "sefd_pmsqe_backward",
+            "sefd_loss_ws_floats", "sefd_loss_forward", "sefd_loss_backward", "sefd_loss_rows_ws_floats", "sefd_loss_rows_forward", "sefd_loss_rows_backward", "sefd_loss_dp_offset", "sefd_loss_dp_finish", "sefd_lms_forward", "sefd_lms_backward", "sefd_fsn_targets", "sefd_fsn_targets_backward", "sefd_norm_ws_floats", "sefd_norm_forward", "sefd_norm_backward", "sefd_unfold_forward", "sefd_unfold_backward", "sefd_mix_snr", "sefd_composite_ws_bytes", "sefd_composite_frames", "sefd_stoi_ws_bytes", "sefd_stoi_gpu", "sefd_stoi_ws_bytes_ex", "sefd_stoi_gpu_ex", "sefd_stoi_backward", "sefd_pmsqe_table_floats", "sefd_pmsqe_ws_floats", "sefd_pmsqe_forward", "sefd_pmsqe_backward",
             "sefd_adam_step", "sefd_adam_step_guarded", "sefd_adam_step_guarded_dp", "sefd_plan_status_poison", "sefd_grad_norm_ws_floats", "sefd_grad_norm", "sefd_optim_step", "sefd_plan_status_word", "sefd_plan_status", "sefd_plan_status_set", "sefd_nchw_cl",
             "sefd_tuning_set", "sefd_tuning_get", "sefd_tuning_clear"]

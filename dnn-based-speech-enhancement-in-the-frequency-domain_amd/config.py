@@ -17,7 +17,7 @@ if chkpt_model is not None:
 # option lists the current setting indexes into (config.py:22-27)
 model_list = ['DCCRN', 'CRN', 'FullSubNet']
 loss_list = ['MSE', 'SDR', 'SI-SNR', 'SI-SDR']
-perceptual_list = [False, 'LMS', 'PMSQE']
+perceptual_list = [False, 'LMS', 'PMSQE', 'STOI', 'ESTOI']
 lstm_type = ['real', 'complex']
 main_net = ['LSTM', 'GRU']
 mask_type = ['Direct(None make)', 'E', 'C', 'R']
@@ -74,6 +74,8 @@ weight_decay = 0.0          # non-zero: on the weights only, through model.get_p
 amsgrad = False
 max_grad_norm = None        # a number: global-norm gradient clipping inside the fused step (torch.nn.utils.clip_grad_norm_'s formula)
 gpu_stoi = False            # True: on a cuda DEVICE the validation loop's scorers="default" scores STOI on the GPU (tools_for_estimate.stoi_batch) under the host PESQ
+stoi_loss_weight = 1.0      # perceptual = 'STOI' / 'ESTOI' (not in the reference): the term is stoi_loss_weight * (1 - mean STOI), in [0, weight] beside a main loss
+                            # in dB; loss = (main + perceptual) / 2 is kept, so this weight is how the user balances the two
 train_data_path = None      # [N, 2, L] .npy files of (noisy, clean) pairs; dataloader.py:63-71 has placeholder paths
 valid_data_path = None
 test_data_path = None

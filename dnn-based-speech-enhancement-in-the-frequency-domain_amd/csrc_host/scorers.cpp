@@ -65,7 +65,27 @@ void fft(std::vector<std::complex<double>>& a) {            // in-place radix-2,
   }
 }
 
-double stoi_one(const float* clean, const float* est, int n, int fs) {
+// Extended STOI of one segment: x, y [15][30] are normalised in place, rows (band over time) first, then columns (frame over bands)
+void row_col_normalize(double (*a)[kSeg]) {
+  for (int b = 0; b < kBands; ++b) {
+    double mean = 0, nn = 0;
+    for (int t = 0; t < kSeg; ++t) mean += a[b][t];
+    mean /= kSeg;
+    for (int t = 0; t < kSeg; ++t) { a[b][t] -= mean; nn += a[b][t] * a[b][t]; }
+    const double N = std::sqrt(nn);
+    for (int t = 0; t < kSeg; ++t) a[b][t] = a[b][t] / (N + kEps);
+  }
+  for (int t = 0; t < kSeg; ++t) {
+    double mean = 0, nn = 0;
+    for (int b = 0; b < kBands; ++b) mean += a[b][t];
+    mean /= kBands;
+    for (int b = 0; b < kBands; ++b) { a[b][t] -= mean; nn += a[b][t] * a[b][t]; }
+    const double N = std::sqrt(nn);
+    for (int b = 0; b < kBands; ++b) a[b][t] = a[b][t] / (N + kEps);
+  }
+}
+
+double stoi_one(const float* clean, const float* est, int n, int fs, bool extended) {
   std::vector<double> x(clean, clean + n), y(est, est + n);
   if (fs != kFs) {
     const std::vector<double> h = resample_window(kFs, fs);
@@ -116,10 +136,29 @@ double stoi_one(const float* clean, const float* est, int n, int fs) {
       yt[(size_t)b * nf + f] = std::sqrt(sy);
     }
   }
+  const int J = nf - kSeg + 1;
+  if (extended) {
+    // ---- extended STOI: correlation of the row- and column-normalised segments
+    double total = 0;
+    for (int m = 0; m < J; ++m) {
+      double xs[kBands][kSeg], ys[kBands][kSeg];
+      for (int b = 0; b < kBands; ++b)
+        for (int t = 0; t < kSeg; ++t) { xs[b][t] = xt[(size_t)b * nf + m + t]; ys[b][t] = yt[(size_t)b * nf + m + t]; }
+      row_col_normalize(xs);
+      row_col_normalize(ys);
+      double seg = 0;
+      for (int t = 0; t < kSeg; ++t) {
+        double s = 0;
+        for (int b = 0; b < kBands; ++b) s += xs[b][t] * ys[b][t];
+        seg += s;
+      }
+      total += seg / kSeg;
+    }
+    return total / (double)J;
+  }
   // ---- clipped, normalised correlation over 30-frame segments
   const double clip = 1.0 + std::pow(10.0, -kBeta / 20.0);
   double total = 0;
-  const int J = nf - kSeg + 1;
   for (int m = 0; m < J; ++m)
     for (int b = 0; b < kBands; ++b) {
       const double* xs = &xt[(size_t)b * nf + m];
@@ -154,7 +193,14 @@ extern "C" {
 // STOI of `B` utterance pairs of `n` samples each (row-major [B][n] float32) at sampling rate fs; one score per utterance.
 int32_t sefd_stoi_batch(const float* clean, const float* est, int32_t B, int32_t n, int32_t fs, double* out, int32_t nthreads) {
   if (!clean || !est || !out || B < 1 || n < 1 || fs < 1) return -1;
-  parallel_for(B, nthreads, [&](int b) { out[b] = stoi_one(clean + (int64_t)b * n, est + (int64_t)b * n, n, fs); });
+  parallel_for(B, nthreads, [&](int b) { out[b] = stoi_one(clean + (int64_t)b * n, est + (int64_t)b * n, n, fs, false); });
+  return 0;
+}
+
+// The same with a flag: extended != 0 scores extended STOI (Jensen & Taal 2016) on the same framing, cut and band envelopes.
+int32_t sefd_stoi_batch_ex(const float* clean, const float* est, int32_t B, int32_t n, int32_t fs, int32_t extended, double* out, int32_t nthreads) {
+  if (!clean || !est || !out || B < 1 || n < 1 || fs < 1) return -1;
+  parallel_for(B, nthreads, [&](int b) { out[b] = stoi_one(clean + (int64_t)b * n, est + (int64_t)b * n, n, fs, extended != 0); });
   return 0;
 }
 

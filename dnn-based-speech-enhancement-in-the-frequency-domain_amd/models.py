@@ -287,12 +287,12 @@ class _SefdModule(nn.Module):
     # ---- fused training step (what trainer.model_train does per batch, trainer.py:27-39) ---------------------
     def train_step(self, inputs, targets, optimizer, loss_kind=None, exchange=None, perceptual=None):
         """forward -> loss -> backward -> Adam with no autograd bookkeeping over the network; returns the loss as a 0-d device tensor.
-        perceptual = 'LMS' | 'PMSQE': the step of model_perceptual_train (trainer.py:45-82), loss = (main + perceptual) / 2 (DCCRN only:
+        perceptual = 'LMS' | 'PMSQE' | 'STOI' | 'ESTOI': the step of model_perceptual_train (trainer.py:45-82), loss = (main + perceptual) / 2 (DCCRN only:
         CRN + perceptual crashes in the reference)."""
         from .optim import Adam
         if perceptual and not hasattr(self, "_stft_ref"):
             raise NotImplementedError("perceptual losses are defined for DCCRN only (models.py:303-314)")
-        if perceptual not in (None, False, "LMS", "PMSQE"):
+        if perceptual not in (None, False, "LMS", "PMSQE", "STOI", "ESTOI"):
             raise ValueError(f"unknown perceptual loss {perceptual!r}")
         if not isinstance(optimizer, Adam):
             raise TypeError("train_step needs sefd_amd.optim.Adam (flat fused Adam)")
@@ -365,9 +365,12 @@ class _SefdModule(nn.Module):
             half = torch.full((1,), 0.5, dtype=torch.float32, device=inputs.device)
             tfl.loss_backward_raw(kind, rt.out_wav, targets, ws, half, rt.g_wav, stream)
             with torch.enable_grad():                    # the loss kernels' own autograd wrappers on leaf copies of the outputs
-                if perceptual == "PMSQE":
+                if perceptual in ("PMSQE", "STOI", "ESTOI"):     # waveform-domain terms
                     est = rt.out_wav.detach().requires_grad_()
-                    perc = tfl.get_array_pmsqe_loss(targets, est)
+                    if perceptual == "PMSQE":
+                        perc = tfl.get_array_pmsqe_loss(targets, est)
+                    else:
+                        perc = tfl.stoi_loss(targets, est, cfg.fs, extended=perceptual == "ESTOI")
                     (perc * 0.5).backward()
                     rt.g_wav.add_(est.grad)
                 else:
@@ -829,6 +832,8 @@ class DCCRN(_SefdModule):
                 return tfl.lms_from_spectra(clean_real, clean_imag, real_spec, img_spec)
             if cfg.perceptual == 'PMSQE':
                 return tfl.get_array_pmsqe_loss(target, estimated)       # models.py:313-314 (third-party arithmetic: parity unpinned)
+            if cfg.perceptual in ('STOI', 'ESTOI'):                      # not in the reference: 1 - STOI of the GPU scorer
+                return tfl.stoi_loss(target, estimated, cfg.fs, extended=cfg.perceptual == 'ESTOI')
             raise ValueError(f"unknown cfg.perceptual {cfg.perceptual!r}")
         return self._main_loss(estimated, target)
 

@@ -11,7 +11,7 @@ through ctypes (no dispatcher hop inside the fused train step); `tests/test_gpu_
     torch.ops.sefd.adam_step_(param, grad, m, v, step, ...)   torch.optim.Adam.step on flat fp32 buffers, in place
     torch.ops.sefd.mix_snr(speech, bank, start, snr_db, q)   generate_noisy_data.py:46-67 on the GPU
     torch.ops.sefd.composite_measures(clean, enh, fs)         composite.m frame analysis: [B, 3] fp64 (trimmed LLR, trimmed WSS, segSNR)
-    torch.ops.sefd.stoi(clean, enh, fs)                       STOI per utterance: [B] fp64 (tools_for_estimate.stoi_batch)
+    torch.ops.sefd.stoi(clean, enh, fs, extended=False)       STOI / ESTOI per utterance: [B] fp64, differentiable in enh (tools_for_estimate.stoi_batch)
     torch.ops.sefd.plan_run(handle, phase, arenas)           one phase (0 forward, 1 backward) of a planned model: sefd_plan_run
     torch.ops.sefd.basemodel_norm(x, kind, sample_len)        BaseModel's seven norms (tools_for_model.py:881-1104) by number, differentiable w.r.t. x
     torch.ops.sefd.unfold(x, n)                               BaseModel.unfold (tools_for_model.py:806-837), differentiable w.r.t. x
@@ -265,16 +265,38 @@ def _(clean, enhanced, fs):
 
 
 @torch.library.custom_op("sefd::stoi", mutates_args=())
-def stoi(clean: torch.Tensor, enhanced: torch.Tensor, fs: int) -> torch.Tensor:
+def stoi(clean: torch.Tensor, enhanced: torch.Tensor, fs: int, extended: bool = False) -> torch.Tensor:
     """STOI of a batch on the device (sefd_stoi_gpu, the arithmetic of tools_for_estimate.cal_stoi): clean / enhanced [B, L] at rate fs ->
-    fp64 [B]."""
+    fp64 [B]; extended=True: extended STOI.  Differentiable in `enhanced` (sefd_stoi_backward)."""
     from .tools_for_estimate import stoi_batch
-    return stoi_batch(clean, enhanced, fs)
+    return stoi_batch(clean, enhanced, fs, extended)
 
 
 @stoi.register_fake
-def _(clean, enhanced, fs):
+def _(clean, enhanced, fs, extended=False):
     return clean.new_empty((clean.shape[0],), dtype=torch.float64)
+
+
+def _stoi_setup(ctx, inputs, output):
+    clean, enhanced, fs, extended = inputs
+    if ctx.needs_input_grad[0]:
+        raise NotImplementedError("sefd::stoi differentiates `enhanced` only: `clean` requires a gradient, and the clean signal (with the "
+                                  "frames it selects) is a constant of the score")
+    ctx.save_for_backward(clean, enhanced)
+    ctx.fs, ctx.extended = fs, extended
+
+
+def _stoi_bwd(ctx, g):
+    # the op returns the scores alone, so the backward scores again with the keep flag (tools_for_loss.stoi_loss holds its workspace instead)
+    from . import tools_for_estimate as te
+    clean, enhanced = ctx.saved_tensors
+    flags = te.STOI_KEEP | (te.STOI_EXTENDED if ctx.extended else 0)
+    _, ws = te.stoi_forward_raw(clean, enhanced, ctx.fs, flags)
+    grad = te.stoi_backward_raw(enhanced.shape[0], enhanced.shape[1], ctx.fs, flags, ws, g)
+    return None, grad.to(enhanced.dtype), None, None
+
+
+stoi.register_autograd(_stoi_bwd, setup_context=_stoi_setup)
 
 
 # ---------------------------------------------------------------------------------------------- planned models

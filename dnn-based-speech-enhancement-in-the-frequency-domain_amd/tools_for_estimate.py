@@ -45,13 +45,15 @@ def lib():
         L = C.CDLL(LIB_PATH)
         L.sefd_stoi_batch.restype = C.c_int32
         L.sefd_stoi_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+        L.sefd_stoi_batch_ex.restype = C.c_int32
+        L.sefd_stoi_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
         L.sefd_pesq_batch.restype = C.c_int32
         L.sefd_pesq_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
         _lib = L
     return _lib
 
 
-EXPORTED = ["sefd_stoi_batch", "sefd_pesq_batch"]
+EXPORTED = ["sefd_stoi_batch", "sefd_stoi_batch_ex", "sefd_pesq_batch"]
 
 
 def _pair(est, clean):
@@ -62,11 +64,15 @@ def _pair(est, clean):
     return est, clean
 
 
-def cal_stoi(estimated_speechs, clean_speechs, nthreads=0):
-    """tools_for_estimate.py:91-99: STOI(clean, estimated, cfg.fs, extended=False) per utterance."""
+def cal_stoi(estimated_speechs, clean_speechs, nthreads=0, *, extended=False):
+    """tools_for_estimate.py:91-99: STOI(clean, estimated, cfg.fs, extended=False) per utterance; extended=True scores extended STOI
+    (Jensen & Taal 2016, sefd_stoi_batch_ex), which the reference never asks for."""
     est, clean = _pair(estimated_speechs, clean_speechs)
     out = np.zeros(est.shape[0], dtype=np.float64)
-    rc = lib().sefd_stoi_batch(clean.ctypes.data, est.ctypes.data, est.shape[0], est.shape[1], int(cfg.fs), out.ctypes.data, nthreads)
+    if extended:
+        rc = lib().sefd_stoi_batch_ex(clean.ctypes.data, est.ctypes.data, est.shape[0], est.shape[1], int(cfg.fs), 1, out.ctypes.data, nthreads)
+    else:
+        rc = lib().sefd_stoi_batch(clean.ctypes.data, est.ctypes.data, est.shape[0], est.shape[1], int(cfg.fs), out.ctypes.data, nthreads)
     if rc != 0:
         raise RuntimeError(f"sefd_stoi_batch failed ({rc})")
     return list(out)
@@ -123,12 +129,55 @@ def composite_frames(clean, enhanced, fs=None):
     return out
 
 
-def stoi_batch(clean, enhanced, fs=None):
+STOI_EXTENDED, STOI_KEEP = 1, 2        # flags of sefd_stoi_gpu_ex (include/sefd.h)
+
+
+def stoi_forward_raw(clean, enhanced, fs, flags):
+    """sefd_stoi_gpu_ex on the current stream: (scores fp64 [B], workspace).  With STOI_KEEP the workspace is what sefd_stoi_backward reads."""
+    import torch
+    from . import _lib
+    if not (clean.is_cuda and enhanced.is_cuda):
+        raise RuntimeError("sefd stoi_batch runs on the MI355X only (cuda tensors); there is no CPU fallback (cal_stoi is the host scorer)")
+    if clean.dim() != 2 or clean.shape != enhanced.shape:
+        raise ValueError(f"stoi: clean and enhanced must both be [B, L], got {tuple(clean.shape)} and {tuple(enhanced.shape)}")
+    clean = clean.detach().float().contiguous()
+    enhanced = enhanced.detach().float().contiguous()
+    B, L = clean.shape
+    L_ = _lib.lib()
+    nbytes = L_.sefd_stoi_ws_bytes_ex(B, L, fs, flags)
+    if nbytes < 0:
+        raise ValueError(f"stoi: unsupported shape / rate (B={B}, L={L}, fs={fs}): code {nbytes} (include/sefd.h sefd_stoi_gpu)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=clean.device)
+    out = torch.empty(B, dtype=torch.float64, device=clean.device)
+    rc = L_.sefd_stoi_gpu_ex(clean.data_ptr(), enhanced.data_ptr(), B, L, fs, flags, ws.data_ptr(), out.data_ptr(),
+                             torch.cuda.current_stream(clean.device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f"sefd_stoi_gpu_ex failed ({rc})")
+    return out, ws
+
+
+def stoi_backward_raw(B, L, fs, flags, ws, grad_out):
+    """sefd_stoi_backward on the current stream: grad_out fp64 [B] -> d / d enhanced, fp32 [B, L]; `ws` from stoi_forward_raw with STOI_KEEP."""
+    import torch
+    from . import _lib
+    grad_out = grad_out.detach().to(torch.float64).contiguous()
+    grad = torch.empty((B, L), dtype=torch.float32, device=ws.device)
+    rc = _lib.lib().sefd_stoi_backward(B, L, fs, flags, ws.data_ptr(), grad_out.data_ptr(), grad.data_ptr(),
+                                       torch.cuda.current_stream(ws.device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f"sefd_stoi_backward failed ({rc})")
+    return grad
+
+
+def stoi_batch(clean, enhanced, fs=None, extended=False):
     """STOI on the GPU (sefd_stoi_gpu; the arithmetic of cal_stoi / csrc_host/scorers.cpp stoi_one in fp64): cuda [B, L] clean / enhanced at
-    rate fs (default cfg.fs) -> cuda fp64 [B], launched on the current stream; nothing waits for the result."""
+    rate fs (default cfg.fs) -> cuda fp64 [B], launched on the current stream; nothing waits for the result.  extended=True: extended STOI
+    (the arithmetic of cal_stoi(..., extended=True))."""
     import torch
     from . import _lib
     fs = int(cfg.fs if fs is None else fs)
+    if extended:
+        return stoi_forward_raw(clean, enhanced, fs, STOI_EXTENDED)[0]
     if not (clean.is_cuda and enhanced.is_cuda):
         raise RuntimeError("sefd stoi_batch runs on the MI355X only (cuda tensors); there is no CPU fallback (cal_stoi is the host scorer)")
     if clean.dim() != 2 or clean.shape != enhanced.shape:

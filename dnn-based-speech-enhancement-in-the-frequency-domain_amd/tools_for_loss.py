@@ -354,3 +354,39 @@ def get_array_pmsqe_loss(clean_array, est_array):
     if clean_array.dim() == 3:
         clean_array, est_array = clean_array.flatten(1), est_array.flatten(1)
     return _PMSQE.apply(clean_array, est_array, bool(getattr(cfg, "pmsqe_power", False)))
+
+
+# ------------------------------------------------------------------------------------------ STOI / ESTOI (not in the reference)
+class _STOI(torch.autograd.Function):
+    """weight * (1 - mean_b d_b) of the GPU scorer (csrc/stoi.hip): the forward keeps its workspace for sefd_stoi_backward.  Differentiable
+    once, with respect to the estimate; the clean signal and the frames it selects are constants."""
+
+    @staticmethod
+    def forward(ctx, clean, est, fs, extended, weight):
+        from . import tools_for_estimate as te
+        flags = te.STOI_KEEP | (te.STOI_EXTENDED if extended else 0)
+        d, ws = te.stoi_forward_raw(clean, est, fs, flags)
+        ctx.t = (est.shape[0], est.shape[1], fs, flags, ws, weight)
+        ctx.mark_non_differentiable(d)
+        return (weight * (1.0 - d.mean())).float(), d
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _gd):
+        from . import tools_for_estimate as te
+        B, L, fs, flags, ws, weight = ctx.t
+        grad_out = (g.to(torch.float64) * (-weight / B)).expand(B)
+        return None, te.stoi_backward_raw(B, L, fs, flags, ws, grad_out), None, None, None
+
+
+def stoi_loss(clean, est, fs=None, extended=False):
+    """cfg.stoi_loss_weight * (1 - mean over the batch of STOI(clean, est)) as an fp32 scalar, differentiable in `est` (sefd_stoi_gpu_ex /
+    sefd_stoi_backward, fp64 inside): cuda [B, L] waves at rate fs (default cfg.fs).  extended=True: extended STOI."""
+    if clean.requires_grad:
+        raise NotImplementedError("stoi_loss differentiates the estimate only: `clean` requires a gradient, and the clean signal (with the "
+                                  "frames it selects) is a constant of the loss")
+    if not (clean.is_cuda and est.is_cuda):
+        raise RuntimeError("sefd STOI loss runs on the MI355X only (cuda tensors); there is no CPU fallback")
+    if est.dim() != 2 or clean.shape != est.shape:
+        raise ValueError("stoi_loss takes two [B, L] wave batches")
+    return _STOI.apply(clean, est, int(cfg.fs if fs is None else fs), bool(extended), float(cfg.stoi_loss_weight))[0]

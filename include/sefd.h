@@ -237,6 +237,30 @@ int32_t sefd_composite_frames(const float* clean, const float* enhanced, int32_t
 #define SEFD_STOI_MAX_SAMPLES (1 << 26)
 int64_t sefd_stoi_ws_bytes(int32_t B, int32_t L, int32_t fs);
 int32_t sefd_stoi_gpu(const float* clean, const float* est, int32_t B, int32_t L, int32_t fs, void* ws, double* out, void* stream);
+/* The same scorer with flags.  Bit 0 (SEFD_STOI_EXTENDED): extended STOI (Jensen & Taal 2016) - same resampling, silent-frame cut, band
+ * envelopes and 30-frame segments, then per segment the 15 x 30 clean and estimate matrices are normalised alike, every row (band over time)
+ * to zero mean and divided by (norm + eps), then every column (frame over bands) likewise; the segment's score is sum(x_n y_n) / 30 and out[b]
+ * the mean over the segments (1e-5 below 30 frames); no norm-ratio scaling, no clip; one wave per segment, fixed summation order, no atomics.
+ * Bit 1 (SEFD_STOI_KEEP): the workspace is left as sefd_stoi_backward reads it and is larger (the frame -> kept-position map, the estimate at
+ * 10 kHz in fp64, and the backward's own buffers, 450 doubles per segment the largest).  flags == 0 is sefd_stoi_gpu, bit for bit; any other
+ * bit set is -1.  sefd_stoi_ws_bytes_ex sizes the workspace for the same flags (host arithmetic, the same negative codes).
+ *
+ * sefd_stoi_backward: the gradient of sum_b grad_out[b] out[b] with respect to the estimate, after sefd_stoi_gpu_ex ran with the keep bit on
+ * the same (B, L, fs, flags, ws).  grad_out fp64 device [B]; grad_est fp32 device [B][L], every element written, fp64 arithmetic rounded
+ * once at the store.  The clean signal, the selection of frames it decides and the resampling filter are constants.  Stages in reverse, all
+ * gathers (no atomics; bit-identical from run to run, independent of the rest of the batch): per-segment cotangents of the estimate's band
+ * envelopes (STOI through the clip - a clipped entry passes nothing directly - the scale c and the normalisation; ESTOI through both
+ * normalisations), their sum per envelope element in ascending segment order, per compacted frame the spectrum again and the
+ * inverse-direction 512-point transform of G[k] = g_yt Y[k] / yt times the window, per 10 kHz sample its at most two kept frames, and the
+ * transpose of the resampler (at 10 kHz the cast alone).  Samples that only dropped frames cover, the last 128 compacted samples and an
+ * utterance scored 1e-5 get exactly 0.  Where torch would give NaN - a band envelope that is exactly 0 under the square root, a norm that
+ * is exactly 0 under a division - the gradient through that term is 0.  Enqueued on `stream`; the host never waits, allocates or frees.
+ * Returns 0, -1 bad arguments (NULL, the keep bit missing, unknown bits), -2 launch failure, -3 / -4 as sefd_stoi_gpu. */
+#define SEFD_STOI_EXTENDED 1
+#define SEFD_STOI_KEEP 2
+int64_t sefd_stoi_ws_bytes_ex(int32_t B, int32_t L, int32_t fs, int32_t flags);
+int32_t sefd_stoi_gpu_ex(const float* clean, const float* est, int32_t B, int32_t L, int32_t fs, int32_t flags, void* ws, double* out, void* stream);
+int32_t sefd_stoi_backward(int32_t B, int32_t L, int32_t fs, int32_t flags, void* ws, const double* grad_out, float* grad_est, void* stream);
 int32_t sefd_fsn_targets(const float* noisy_c64, const float* clean_c64, int64_t n, float* mag, float* phase, float* cirm, void* stream);
 /* Its backward, one pass over the interleaved complex inputs (fp32 device, n bins).  Cotangents g_mag, g_phase [n] and g_cirm [n][2], each NULL for
  * "no gradient"; d_noisy / d_clean [n][2] (NULL: not wanted) receive (dL/dre, dL/dim) of that argument and are written once, no accumulation.
